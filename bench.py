@@ -30,8 +30,14 @@ clamp as one kernel over all N (`ms_per_step_sh_over_all_gaussians`), with the c
 
 Rank 0 prints ONE JSON line; see the task contract for the fields.  `roofline` describes the
 dominant kernel (compositing backward) with its duration measured live by HIP events on the
-launch stream; `cpu_baseline` times oracle/gsplat_oracle.c (the CPU restatement, "port") on the
-host cores for the same workload.
+launch stream.
+
+A plain run does what the headline needs and nothing more: set-up, the W + K steps in both launch modes, the line.  `--full` adds
+everything else the line can carry, each of it a run of its own: the graph timings on the tight lists / with PyTorch's activation /
+with SH over all Gaussians, the live timing of every entry point (`roofline.entry_points`), the forward-only rate and the shipped
+and MTGS-style cells (`also`), and `cpu_baseline` (oracle/gsplat_oracle.c, the CPU restatement, "port", on the host cores for the
+same workload).  `--dump-outputs DIR` writes what the timed path returned in its last step (image, alpha, every parameter
+gradient; per-Gaussian rows and, past 48 MiB, pixels as a fixed seeded sample) as DIR/<name>.npy in float32, 64 MiB at most.
 """
 from __future__ import annotations
 
@@ -151,7 +157,14 @@ def parse_args():
                                                              "the kernel trace then holds the default call's kernels only)")
     ap.add_argument("--no-also", action="store_true", help="skip the untimed extras (forward-only rate, shipped 7-channel cells): "
                                                             "profiling runs, so that the trace holds the headline step only")
-    return ap.parse_args()
+    ap.add_argument("--full", action="store_true", help="besides the headline: the other graph timings, the entry-point timings, the "
+                                                         "untimed extras and the CPU baseline (each trimmed by --no-tight / --no-also / "
+                                                         "--cpu-steps 0)")
+    ap.add_argument("--dump-outputs", metavar="DIR", help="write the outputs of the timed path's last step as DIR/<name>.npy")
+    args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
+    return args
 
 
 def build_inputs(args, rank, device):
@@ -291,6 +304,35 @@ def make_step(args, dev, world):
 
     info_box["exchange"] = exchange
     return step, step_fwd, all_params, info_box
+
+
+DUMP_BYTES = 64 << 20       # --dump-outputs: the most the files may hold together
+DUMP_GAUSSIANS = 1 << 16    # rows of every per-Gaussian gradient in the dump (all of them are 0.5 GB at 2M Gaussians)
+
+
+def _rows(t, n, seed):
+    """t [R, ...] as a float32 host array: all R rows when R <= n, else n rows drawn by a seeded permutation, in index order, so
+    that every run and every build dumps the same rows."""
+    t = t.detach()
+    if t.shape[0] > n:
+        idx = torch.randperm(t.shape[0], generator=torch.Generator().manual_seed(seed))[:n].sort().values
+        t = t[idx.to(t.device)]
+    return t.float().cpu().numpy()
+
+
+def output_arrays(render, alpha, grads):
+    """What the step handed its caller: image and alpha (every pixel while both fit into 3/4 of DUMP_BYTES, else a seeded sample of
+    pixels) and the gradient of every parameter (per-Gaussian ones: a seeded sample of DUMP_GAUSSIANS rows; the viewmat's whole)."""
+    out = {}
+    n_pix = (DUMP_BYTES * 3 // 4) // (4 * (render.shape[-1] + alpha.shape[-1]))
+    for name, img in (("render", render), ("alpha", alpha)):
+        a = _rows(img.reshape(-1, img.shape[-1]), n_pix, 1)
+        out[name] = a.reshape(img.shape) if a.size == img.numel() else a
+    for name, g in grads.items():
+        if g is not None:
+            out[f"grad_{name}"] = g.detach().float().cpu().numpy() if name == "viewmat" else _rows(g, DUMP_GAUSSIANS, 2)
+    assert sum(a.nbytes for a in out.values()) <= DUMP_BYTES
+    return out
 
 
 def mtgs_like_iteration_cells():
@@ -622,7 +664,7 @@ def main():
     t0 = time.perf_counter()
     try:
         for _ in range(args.steps):
-            step()
+            last = step()
         torch.cuda.synchronize()
         barrier()
         torch.cuda.synchronize()
@@ -631,6 +673,12 @@ def main():
     elapsed = time.perf_counter() - t0
     if info_box.get("overflow") is not None and bool(info_box["overflow"]):
         fail("timed steps", RuntimeError(f"static exchange: a rank had more wire rows than the capacity {info_box['static_cap']}"))
+    # the outputs of each launch mode's last timed step, taken before anything else runs the step (--dump-outputs); `last` holds the
+    # step's autograd graph and must not outlive this (see the detached info below)
+    grad_names = ["means", "quats", "scales", "opacities", "coeffs" if args.variant == "mtgs" else "colors", "viewmat"]
+    dump = args.dump_outputs and rank == 0
+    outputs = {"eager": output_arrays(*last, dict(zip(grad_names, (p.grad for p in all_params))))} if dump else {}
+    last = None
     kernel_ms = [t for name in DOMINANT for t in _lib.timed_ms().get(name, [])]
     _lib.time_calls(())
     # (detached: the info of a step holds means2d and with it the step's autograd graph, whose AccumulateGrad nodes would be reused
@@ -671,7 +719,7 @@ def main():
                 torch.cuda.synchronize()
                 g = torch.cuda.CUDAGraph()
                 with gm, torch.cuda.graph(g):
-                    step()
+                    captured = step()
             overflow, n_l = info_box["info"]["overflow"], info_box["info"]["n_listed"]
             info_box["info"] = None
             for _ in range(args.warmup):
@@ -684,27 +732,30 @@ def main():
             t1 = time.perf_counter()
             if bool(overflow):
                 raise RuntimeError("the captured frame exceeded its capacities")
-            return t1 - t0, int(n_l)
+            return t1 - t0, int(n_l), captured
         finally:
             info_box["capture"] = False
 
     if world == 1 and args.launch == "graph":
         try:
-            elapsed_graph, _ = graph_time(False)
+            elapsed_graph, _, captured = graph_time(False)
+            if dump:        # (the replays' outputs: the captured step's output tensors and the gradients it allocated)
+                outputs["graph"] = output_arrays(*captured, dict(zip(grad_names, (p.grad for p in all_params))))
+            captured = None
             if elapsed_graph < elapsed:      # the line carries the faster of the two launch modes and names it; the other is beside it
                 elapsed, launch = elapsed_graph, "graph"
         except Exception as e:      # noqa: BLE001  (the eager figure stands)
             graph_error = f"{type(e).__name__}: {e}"[:300]
             print(f"[bench] graph launch failed, reporting the eager loop: {graph_error}", file=sys.stderr)
         try:        # beside the headline, never the headline: the same step on the opt-in tight tile lists
-            if not args.no_tight:
-                elapsed_graph_tight, n_listed_tight = graph_time(True)
+            if args.full and not args.no_tight:
+                elapsed_graph_tight, n_listed_tight, _ = graph_time(True)
         except Exception as e:      # noqa: BLE001
             print(f"[bench] tight-lists graph failed: {type(e).__name__}: {e}"[:300], file=sys.stderr)
         try:        # ... and with the colour activation left to PyTorch (what round 5's line measured)
-            if not args.no_tight and args.variant == "mtgs":
-                elapsed_graph_torch_act, _ = graph_time(False, lazy_sh=False)
-                elapsed_graph_all_sh, _ = graph_time(False, raster=False)
+            if args.full and not args.no_tight and args.variant == "mtgs":
+                elapsed_graph_torch_act, _, _ = graph_time(False, lazy_sh=False)
+                elapsed_graph_all_sh, _, _ = graph_time(False, raster=False)
         except Exception as e:      # noqa: BLE001
             print(f"[bench] torch-activation graph failed: {type(e).__name__}: {e}"[:300], file=sys.stderr)
     info_box["info"] = eager_info
@@ -716,14 +767,16 @@ def main():
         rank_phases = {"render": evs["start"].elapsed_time(evs["rows"]), "exchange": evs["rows"].elapsed_time(evs["end"])}
         if info_box["exchange"] is not None:
             rank_phases.update(info_box["exchange"].phases_ms())
-    # second, UNTIMED pass: every entry point of the step bracketed by HIP events on the launch stream (the events
+    # second, UNTIMED pass (--full): every entry point of the step bracketed by HIP events on the launch stream (the events
     # serialise nothing, but they are kept out of the headline figure)
-    _lib.time_calls(tuple(ENTRY_POINTS))
-    for _ in range(min(args.steps, 8)):
-        step()
-    torch.cuda.synchronize()
-    entry_ms = {n: v for n, v in _lib.timed_ms().items() if v}
-    _lib.time_calls(())
+    entry_ms = {}
+    if args.full:
+        _lib.time_calls(tuple(ENTRY_POINTS))
+        for _ in range(min(args.steps, 8)):
+            step()
+        torch.cuda.synchronize()
+        entry_ms = {n: v for n, v in _lib.timed_ms().items() if v}
+        _lib.time_calls(())
     barrier()
     if world > 1:
         t = torch.tensor([elapsed], dtype=torch.float64, device=device)
@@ -733,7 +786,7 @@ def main():
     # outside the timed region: the forward-only rate SURVEY.md section 8(d) asks to be reported beside the headline
     # (what eval / the viewer run: the same calls under no_grad)
     fwd_ms = None
-    if world == 1 and not args.no_also:
+    if world == 1 and args.full and not args.no_also:
         params_were = [p.requires_grad for p in all_params]
         with torch.no_grad():
             for _ in range(2):
@@ -948,9 +1001,9 @@ def main():
                              "and the `valu` block come from the committed rocprofv3 --pmc passes named in counters_from (null when none "
                              "matches this library's hot-path ABI version)",
                      "counters_from": counters_from,
-                     "entry_points": entry_points,
-                     "entry_points_note": "measured in THIS run: HIP events on the launch stream around every C-ABI entry point of the "
-                                          "step, in a second untimed pass; algorithmic bytes from this run's (N, n_vis, M)",
+                     "entry_points": entry_points if args.full else None,
+                     "entry_points_note": "measured in THIS run (--full; null without): HIP events on the launch stream around every C-ABI "
+                                          "entry point of the step, in a second untimed pass; algorithmic bytes from this run's (N, n_vis, M)",
                      "kernels": kernels,
                      "kernels_note": "per kernel: algorithmic bytes of this run; *_committed = builder-held rocprofv3 numbers from "
                                      "counters_from, not measured in this run",
@@ -1005,8 +1058,13 @@ def main():
             out["also"].update(sh_degree_cell(args, dev))
             out["also"].update(mtgs_like_iteration_cells())
             out["also"].update(c1_c2_cells(args, device))      # (behind the child processes: its CPU leg starts the OpenMP pool)
-    if rank == 0 and world == 1 and args.cpu_steps > 0:
+    if rank == 0 and world == 1 and args.full and args.cpu_steps > 0:
         out["cpu_baseline"] = cpu_baseline(args, host, args.cpu_steps)
+    if dump:
+        import numpy as np
+        os.makedirs(args.dump_outputs, exist_ok=True)
+        for name, a in outputs[launch].items():
+            np.save(os.path.join(args.dump_outputs, f"{name}.npy"), a)
     if rank == 0:
         print(json.dumps(out), flush=True)
     if world > 1:

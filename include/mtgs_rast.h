@@ -880,6 +880,39 @@ int mtgs_vis_color_bwd_dirs(int n_nodes, const mtgs_node_desc *table, int degree
 int mtgs_rows_expand(int64_t N, int width, const int32_t *row_of, const float *rows, int64_t row_stride, float *out,
                      void *stream);
 
+/* ---- WildGaussians appearance colours (config/WildGaussians.py; mtgs_scene_graph.py:308-318, :623-632) ----
+ * Additive block: MTGS_RAST_ABI_VERSION stays 28 and MTGS_RAST_HOT_ABI_VERSION 7 (no existing kernel or signature changes).
+ *   rgb = clamp(features_dc * C0 + 0.5, 0, 1);  x = [rgb | features_rest row[:24] | e];  y = 0.01 * L3(relu(L2(relu(L1(x)))));
+ *   colour = rgb * (1 + y[3:6]) + y[0:3]          (L1: 59 -> 128, L2: 128 -> 128, L3: 128 -> 6, nn.Linear layouts, fp32)
+ * Weights are nn.Linear's: w1 [128, 59], b1 [128], w2 [128, 128], b2 [128], w3 [6, 128], b3 [6]; embedding e [32] (nullable:
+ * zeros).  n_feat, n_embed, n_hidden, n_out must be 27, 32, 128, 6 (anything else: MTGS_EUNSUPPORTED).  Row sets: vis_ids NULL =
+ * DENSE, row r is Gaussian r for r < cap_rows; vis_ids given = row r is Gaussian vis_ids[r] for r < min(totals[0] >> 32, cap_rows)
+ * (the front end's device count, never read on the host).  features_dc row g at features_dc + g * dc_stride (3 floats),
+ * features_rest row g at features_rest + g * rest_stride (its first 24 floats are read).  cap_rows = 0 is a no-op.
+ * mtgs_wild_fwd: the colour of row r to out + r * out_stride (3 floats: a dense [N, 3] tensor, or recs + 8 with stride 16 --
+ * channels 0..2 of the packed records, as mtgs_vis_color_fwd_dirs writes them).  row_flags (nullable, with vis_ids): rows whose
+ * flag is 0 get the colour 0 and nothing of them is read (ColorSource.touch_first).
+ * mtgs_wild_bwd: grad row r at grad + r * grad_stride (3 floats: d L / d colour -- the compaction rows of the compositing
+ * backward, or a dense [N, 3]).  Writes d features_dc (through the clamp mask) to d_dc + g * 3 and d features_rest to
+ * d_rest + g * d_rest_width (24 values, zeros behind them); a row set leaves the other Gaussians' rows alone (zero them first).
+ * h1 and h2 are recomputed.  The weight gradients go to `partials` (mtgs_wild_workspace_bytes(cap_rows)) as one partial sum per
+ * workgroup; mtgs_wild_reduce (same cap_rows) adds them in a fixed order and WRITES d_w1 [128, 59], d_b1, d_w2, d_b2, d_w3,
+ * d_b3 and d_embed [32] (nullable) -- no float atomics: bitwise identical from run to run. */
+int mtgs_wild_workspace_bytes(int64_t cap_rows, size_t *bytes);
+int mtgs_wild_fwd(int64_t cap_rows, const int32_t *vis_ids, const int64_t *totals, const uint8_t *row_flags,
+                  const float *features_dc, int64_t dc_stride, const float *features_rest, int64_t rest_stride,
+                  const float *embedding, const float *w1, const float *b1, const float *w2, const float *b2,
+                  const float *w3, const float *b3, int n_feat, int n_embed, int n_hidden, int n_out, float *out,
+                  int64_t out_stride, void *stream);
+int mtgs_wild_bwd(int64_t cap_rows, const int32_t *vis_ids, const int64_t *totals, const float *grad, int64_t grad_stride,
+                  const float *features_dc, int64_t dc_stride, const float *features_rest, int64_t rest_stride,
+                  const float *embedding, const float *w1, const float *b1, const float *w2, const float *b2,
+                  const float *w3, const float *b3, int n_feat, int n_embed, int n_hidden, int n_out, float *d_dc,
+                  float *d_rest, int64_t d_rest_width, float *partials, size_t ws_bytes, void *stream);
+int mtgs_wild_reduce(int64_t cap_rows, const float *partials, const float *embedding, const float *w1, int n_feat, int n_embed,
+                     int n_hidden, int n_out, float *d_w1, float *d_b1, float *d_w2, float *d_b2, float *d_w3, float *d_b3,
+                     float *d_embed, void *stream);
+
 /* ---- SURVEY.md section 8f, rank 2 (second half): the optimizer step of every Gaussian parameter group in ONE launch ----
  * Reference: one torch.optim.Adam per parameter group with one tensor each (mtgs/scene_model/custom_trainer.py:115-136;
  * groups, learning rates and eps = 1e-15 in mtgs/config/MTGS.py:121-181); the densification moves the moments with their

@@ -145,6 +145,12 @@ _SIGNATURES = {
     "mtgs_vis_color_fwd_dirs": [_i32, _vp, _i32, _vp, _vp, _vp, _vp, _i64, _vp, _vp, _vp, _i64, _vp, _vp, _vp],
     "mtgs_vis_color_bwd_dirs": [_i32, _vp, _i32, _vp, _vp, _vp, _vp, _i64, _vp, _i64, _i32, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp],
     "mtgs_rows_expand": [_i64, _i32, _vp, _vp, _i64, _vp, _vp],
+    "mtgs_wild_workspace_bytes": [_i64, C.POINTER(_sz)],
+    "mtgs_wild_fwd": [_i64, _vp, _vp, _vp, _vp, _i64, _vp, _i64, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i32, _i32, _i32, _i32,
+                      _vp, _i64, _vp],
+    "mtgs_wild_bwd": [_i64, _vp, _vp, _vp, _i64, _vp, _i64, _vp, _i64, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i32, _i32, _i32, _i32,
+                      _vp, _vp, _i64, _vp, _sz, _vp],
+    "mtgs_wild_reduce": [_i64, _vp, _vp, _vp, _i32, _i32, _i32, _i32, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp],
     "mtgs_adam_group_bytes": [],
     "mtgs_adam_block_elems": [],
     "mtgs_adam_block_rows": [],

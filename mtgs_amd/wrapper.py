@@ -1042,6 +1042,7 @@ class _FusedRasterization(torch.autograd.Function):
             # colours, and one pass of the compositing DECISIONS (mtgs_blend_touch_packed) flags the Gaussians the frame composites
             # from -- a few percent of the visible ones in an opaque scene.  Peek, SH evaluation and normals work on those alone.
             touch_first = cs is not None and bool(cs.touch_first)
+            wild = cs is not None and getattr(cs, "wild", False)
             # tile lists of this frame (thread-local mode, read once): gsplat's by default; mtgs_bin3_build flags: 1 = tight lists,
             # 2 = sentinel-fill the tail [n_listed, M) of flatten_ids / isect_ids (tight lists, tensors sliced to gsplat's M),
             # 4 = sentinel-fill up to the capacity (graph mode: the tensors are capacity-sized in both list modes), 16 = the frame's
@@ -1051,10 +1052,13 @@ class _FusedRasterization(torch.autograd.Function):
 
             def colours(b, flags):   # colours of the visible Gaussians, straight into their records
                 cap_vis = b["cap_vis"]
-                coef = cs.prepare(vis_rank, cap_vis, b["vis_ids"], totals, row_flags=flags)    # (row-lazy optimizer: up-to-date coefficient rows, compact)
-                call("mtgs_vis_color_fwd_dirs", cs.n_nodes, ptr(cs.table), cs.degree, ptr(cs.cam), ptr(means), ptr(b["vis_ids"]),
-                     ptr(totals), cap_vis, ptr(b["recs"]), ptr(b["vis_mask"]), ptr(coef), 0 if coef is None else coef.stride(0),
-                     ptr(flags), ptr(cs.dirs), st)
+                if wild:             # WildGaussians appearance colours (appearance.WildColorSource, csrc/wild.hip)
+                    cs.colour_rows(b["vis_ids"], totals, cap_vis, b["recs"], flags, st)
+                else:
+                    coef = cs.prepare(vis_rank, cap_vis, b["vis_ids"], totals, row_flags=flags)    # (row-lazy optimizer: up-to-date coefficient rows, compact)
+                    call("mtgs_vis_color_fwd_dirs", cs.n_nodes, ptr(cs.table), cs.degree, ptr(cs.cam), ptr(means), ptr(b["vis_ids"]),
+                         ptr(totals), cap_vis, ptr(b["recs"]), ptr(b["vis_mask"]), ptr(coef), 0 if coef is None else coef.stride(0),
+                         ptr(flags), ptr(cs.dirs), st)
                 if n2c is not None:  # ... and their camera-space normals (channels 3..5)
                     call("mtgs_normals_fwd_rows", cap_vis, ptr(b["vis_ids"]), ptr(totals), ptr(quats), ptr(scales), ptr(means),
                          ptr(n2c), ptr(b["recs"]), 3, ptr(flags), st)
@@ -1249,7 +1253,11 @@ class _FusedRasterization(torch.autograd.Function):
         if _debug_rows is not None:
             _debug_rows.update(G=G, vis_ids=vis_ids, DC=DC, with_depth=with_depth)
         cs = ctx.cs
-        if cs is not None and not getattr(cs, "exchange", False):      # (data-parallel frames: the colour gradient travels as v_rgb in the wire rows)
+        wild_grads = None
+        if cs is not None and getattr(cs, "wild", False):
+            # WildGaussians appearance colours: dense gradients of the source's inputs (22 ..) from the colour columns of the rows
+            wild_grads = cs.backward_rows(ctx.needs_input_grad[22:], vis_ids, totals, n_vis, G, RS, st)
+        elif cs is not None and not getattr(cs, "exchange", False):      # (data-parallel frames: the colour gradient travels as v_rgb in the wire rows)
             # visibility-first colours: d L / d (SH coefficients) of the VISIBLE Gaussians as 192-byte rows; the optimizer takes
             # them through the row map (vis_rank: rank or -1) -- no dense [N, (T,) K, 3] gradient is written
             dense_coeffs = getattr(ctx, "zero_coeffs", None) if cs.autograd else None      # (zeroed by the forward's compositing kernel)
@@ -1359,7 +1367,7 @@ class _FusedRasterization(torch.autograd.Function):
              ptr(dir_rows) if (cs is not None and cs.autograd and cs.dirs is None and n_vis > 0) else None,      # (differentiable view directions: dirs = means - camera position)
              ptr(G) if raw else None, ptr(recs) if (raw and Cn == 1) else None, ptr(vm_part), st)
         d_coeffs = d_campos = None
-        d_more = (None,) * max(len(ctx.needs_input_grad) - 22, 0)
+        d_more = (None,) * max(len(ctx.needs_input_grad) - 22, 0) if wild_grads is None else wild_grads
         if cs is not None and cs.autograd:
             if ctx.graph and cs.dirs is None:
                 raise NotImplementedError("graph_mode: rasterization(sh_degree=...) (dense coefficient gradient)")
@@ -1468,7 +1476,8 @@ def fused_rasterization(means, quats, scales, opacities, colors, viewmats, Ks, b
                                         int(height), float(eps2d), float(near_plane), float(far_plane), float(radius_clip),
                                         bool(calc_compensations), bool(with_depth), bool(expected_depth), bool(absgrad), dp,
                                         color_source, *_sh_inputs(sh_source),
-                                        *(getattr(color_source, "dirs_inputs", None) or ()))
+                                        *(getattr(color_source, "dirs_inputs", None) or ()),
+                                        *(getattr(color_source, "wild_inputs", None) or ()))
     finally:
         _sh_scope.reqs = ()
     (render, alphas, radii, means2d, depths, conics, comps, opac_eff, tiles_per_gauss, isect_ids, flatten_ids,

@@ -913,6 +913,26 @@ int mtgs_wild_reduce(int64_t cap_rows, const float *partials, const float *embed
                      int n_hidden, int n_out, float *d_w1, float *d_b1, float *d_w2, float *d_b2, float *d_w3, float *d_b3,
                      float *d_embed, void *stream);
 
+/* ---- Image metrics of get_metrics_dict (mtgs_scene_graph.py:747-804; mtgs/utils/pnsr.py color_correct, MaskedPSNR) ----
+ * Additive block: MTGS_RAST_ABI_VERSION stays 28 and MTGS_RAST_HOT_ABI_VERSION 7 (no existing kernel or signature changes).
+ * Images are dense [P, 3] fp32 (P = H * W pixels), mask a nullable [P] uint8 (0 = masked out; NULL = every pixel).
+ * mtgs_color_correct: out [P, 3] = color_correct(img * mask, ref * mask, num_iters, eps) -- per channel c, num_iters fits of
+ *   a(x) = [x0^2, x0x1, x0x2, x1^2, x1x2, x2^2, x0, x1, x2, 1] . w_c to ref_c over the rows with unclipped(img_c) & unclipped(x_c)
+ *   & unclipped(ref_c), unclipped(z) = z >= (float)eps && z <= (float)(1 - eps), each followed by x <- clip(a(x) W, 0, 1); fp64
+ *   normal equations solved by Cholesky on the device.  A fit fails when a pivot is <= 1e-12 times its diagonal entry or anything is
+ *   not finite; then out = img * mask (the reference's `except` path).  num_iters = 0 copies img * mask.
+ * mtgs_image_metrics: metrics[5] fp32 = {psnr(pred, gt), psnr(color_correct(pred, gt), gt), depth_RMSE, depth_absRel,
+ *   depth_delta1} over the mask's pixels (PSNR = 10 log10(n / SSE) over the n = 3 * pixels selected elements: NaN when none, inf
+ *   when SSE = 0; the corrected image is never written).  The depth terms use the pixels with 0.1 < lidar < 80 and the mask
+ *   (pred_depth, lidar_depth: [P] fp32, both or neither; NaN when absent or when no pixel is selected).  num_iters = 0: cc = psnr.
+ * Both need a workspace of mtgs_metrics_workspace_bytes(P, num_iters) bytes (8-byte aligned; no initialisation).  P = 0 is a no-op.
+ * Sums are fp64 in a fixed order, without atomics: bitwise reproducible, no host synchronisation (graph-capturable). */
+int mtgs_metrics_workspace_bytes(int64_t P, int num_iters, size_t *bytes);
+int mtgs_color_correct(int64_t P, int num_iters, double eps, const float *img, const float *ref, const uint8_t *mask, float *out,
+                       void *ws, size_t ws_bytes, void *stream);
+int mtgs_image_metrics(int64_t P, int num_iters, double eps, const float *pred, const float *gt, const uint8_t *mask,
+                       const float *pred_depth, const float *lidar_depth, float *metrics, void *ws, size_t ws_bytes, void *stream);
+
 /* ---- SURVEY.md section 8f, rank 2 (second half): the optimizer step of every Gaussian parameter group in ONE launch ----
  * Reference: one torch.optim.Adam per parameter group with one tensor each (mtgs/scene_model/custom_trainer.py:115-136;
  * groups, learning rates and eps = 1e-15 in mtgs/config/MTGS.py:121-181); the densification moves the moments with their

@@ -151,6 +151,9 @@ _SIGNATURES = {
     "mtgs_wild_bwd": [_i64, _vp, _vp, _vp, _i64, _vp, _i64, _vp, _i64, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i32, _i32, _i32, _i32,
                       _vp, _vp, _i64, _vp, _sz, _vp],
     "mtgs_wild_reduce": [_i64, _vp, _vp, _vp, _i32, _i32, _i32, _i32, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp],
+    "mtgs_metrics_workspace_bytes": [_i64, _i32, C.POINTER(_sz)],
+    "mtgs_color_correct": [_i64, _i32, C.c_double, _vp, _vp, _vp, _vp, _vp, _sz, _vp],
+    "mtgs_image_metrics": [_i64, _i32, C.c_double, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _sz, _vp],
     "mtgs_adam_group_bytes": [],
     "mtgs_adam_block_elems": [],
     "mtgs_adam_block_rows": [],

@@ -1,0 +1,94 @@
+"""MTGS's per-step image metrics on the device (csrc/metrics.hip): the colour-corrected PSNR, the PSNR and the lidar depth errors
+that mtgs_scene_graph.py's get_metrics_dict computes on every training step and for every evaluation image.
+
+    cc = color_correct(pred * mask, gt * mask)            # mtgs/utils/pnsr.py color_correct, mask applied as in the MTGS call
+    m = image_metrics(pred, gt, mask, pred_depth=d, lidar_depth=ld)
+    m["psnr"], m["cc_psnr"], m["depth_RMSE"], m["depth_absRel"], m["depth_delta1"]      # 0-dim fp32 device tensors
+
+Forward only, no host reads (graph-capturable), bitwise reproducible.  The SSIM metric takes the loss's arguments
+(use_ssim_on_raw_rgb=True): reuse mtgs_amd.loss.masked_ssim.  LPIPS and DINOv2 stay in PyTorch.
+"""
+from __future__ import annotations
+
+import ctypes as C
+from typing import Dict, Optional
+
+import torch
+from torch import Tensor
+
+from ._lib import call, ptr, require_gpu, stream_of
+from .loss import _mask_u8
+
+_EPS = 0.5 / 255
+
+
+def _check_images(a: Tensor, b: Tensor, names) -> None:
+    if a.dim() != 3:
+        raise ValueError(f"{names[0]} must be [H, W, C], got {tuple(a.shape)}")
+    if a.shape[-1] != 3:
+        raise NotImplementedError(f"{names[0]} has {a.shape[-1]} channels: only 3-channel images are implemented")
+    if a.shape != b.shape:
+        raise ValueError(f"{names[0]} {tuple(a.shape)} and {names[1]} {tuple(b.shape)} must have the same shape")
+
+
+def _image(t: Tensor) -> Tensor:
+    return t.detach().to(torch.float32).contiguous()
+
+
+def _workspace(P: int, num_iters: int, dev) -> Tensor:
+    n = C.c_size_t(0)
+    call("mtgs_metrics_workspace_bytes", P, num_iters, C.byref(n))
+    return torch.empty(n.value, dtype=torch.uint8, device=dev)
+
+
+def color_correct(img: Tensor, ref: Tensor, mask: Optional[Tensor] = None, num_iters: int = 5, eps: float = _EPS) -> Tensor:
+    """The reference's color_correct(img * mask, ref * mask) (or color_correct(img, ref) without a mask) on [H, W, 3] images.
+    If any fit is singular (a Cholesky pivot <= 1e-12 of its diagonal entry) or not finite, returns img * mask unchanged."""
+    _check_images(img, ref, ("img", "ref"))
+    if num_iters < 0:
+        raise ValueError(f"num_iters must be >= 0, got {num_iters}")
+    require_gpu(img, ref, mask)
+    img_c, ref_c = _image(img), _image(ref)
+    H, W = img_c.shape[:2]
+    out = torch.empty_like(img_c)
+    if H * W == 0:
+        return out
+    ws = _workspace(H * W, num_iters, img_c.device)
+    call("mtgs_color_correct", H * W, int(num_iters), float(eps), ptr(img_c), ptr(ref_c), ptr(_mask_u8(mask, H, W)), ptr(out),
+         ptr(ws), ws.numel(), stream_of(img_c))
+    return out
+
+
+def image_metrics(pred: Tensor, gt: Tensor, mask: Optional[Tensor] = None, *, color_corrected: bool = True,
+                  pred_depth: Optional[Tensor] = None, lidar_depth: Optional[Tensor] = None) -> Dict[str, Tensor]:
+    """get_metrics_dict's device metrics under MTGS's keys, as 0-dim fp32 tensors on pred's device:
+    psnr = MaskedPSNR(data_range=1.0)(gt, pred, mask); cc_psnr (color_corrected) = the same of color_correct(pred * mask,
+    gt * mask), without writing the corrected image; depth_RMSE, depth_absRel, depth_delta1 (both depths given) over the pixels
+    with 0.1 < lidar < 80 and the mask.  Empty selections give nan, a zero error gives inf (as torch)."""
+    _check_images(pred, gt, ("pred", "gt"))
+    if (pred_depth is None) != (lidar_depth is None):
+        raise ValueError("pred_depth and lidar_depth must be given together")
+    require_gpu(pred, gt, mask, pred_depth, lidar_depth)
+    pred_c, gt_c = _image(pred), _image(gt)
+    H, W = pred_c.shape[:2]
+    P = H * W
+    depths = None
+    if pred_depth is not None:
+        if pred_depth.numel() != P or lidar_depth.numel() != P:
+            raise ValueError(f"depths must have H * W = {P} elements, got {pred_depth.numel()} and {lidar_depth.numel()}")
+        depths = (pred_depth.detach().to(torch.float32).reshape(H, W).contiguous(),
+                  lidar_depth.detach().to(torch.float32).reshape(H, W).contiguous())
+    num_iters = 5 if color_corrected else 0
+    if P == 0:
+        out = torch.full((5,), float("nan"), dtype=torch.float32, device=pred_c.device)
+    else:
+        out = torch.empty(5, dtype=torch.float32, device=pred_c.device)
+        ws = _workspace(P, num_iters, pred_c.device)
+        call("mtgs_image_metrics", P, num_iters, _EPS, ptr(pred_c), ptr(gt_c), ptr(_mask_u8(mask, H, W)),
+             ptr(depths[0]) if depths else None, ptr(depths[1]) if depths else None, ptr(out), ptr(ws), ws.numel(), stream_of(pred_c))
+    res = {"psnr": out[0]}
+    if color_corrected:
+        res["cc_psnr"] = out[1]
+    if depths is not None:
+        res.update(depth_RMSE=out[2], depth_absRel=out[3], depth_delta1=out[4])
+    return res

@@ -933,6 +933,47 @@ int mtgs_color_correct(int64_t P, int num_iters, double eps, const float *img, c
 int mtgs_image_metrics(int64_t P, int num_iters, double eps, const float *pred, const float *gt, const uint8_t *mask,
                        const float *pred_depth, const float *lidar_depth, float *metrics, void *ws, size_t ws_bytes, void *stream);
 
+/* ---- Geometric loss terms of get_loss_dict (mtgs_scene_graph.py:905-940, 969-981; mtgs/utils/geometric_loss.py:350-388) ----
+ * Additive block: MTGS_RAST_ABI_VERSION stays 28 and MTGS_RAST_HOT_ABI_VERSION 7 (no existing kernel or signature changes).
+ * Images are dense row-major: depth [H, W] fp32, normals [H, W, 3] fp32, mask a nullable [H, W] uint8 (0 = masked out).
+ * K: DEVICE pointer to the 3x3 intrinsics, row-major fp32; fx, fy, cx, cy = K[0], K[4], K[2], K[5] are read by the kernels.
+ * mtgs_depth_normals: out = (1 + n @ diag(1,-1,-1)) / 2 with n = normal_from_depth_image(depth, fx, fy, cx, cy, (W, H), eye(4)):
+ *   P(v,u) = ((u + 0.5 - cx) d / fx, (v + 0.5 - cy) d / fy, d), n = cross(P[v,u+1] - P[v,u-1], P[v-1,u] - P[v+1,u]) divided by
+ *   max(|n|, 1e-12).  The one-pixel border (every pixel when W or H < 3) and zero cross products give 0.5; NaN propagates,
+ *   and a non-finite component spreads NaN to the others as the reference's products with the identity do.
+ * mtgs_depth_normal_loss_fwd: out[4] = {loss, count, L1, TV}, loss = L1 + TV,
+ *   m = (depth > lo) & (depth < hi) & mask, count = count(m), L1 = sum_m |target - pred| / (3 count) (NaN when count = 0),
+ *   TV = mean |pred[:, :-1] - pred[:, 1:]| + mean |pred[:-1] - pred[1:]| when tv != 0 (NaN for an empty difference), else 0.
+ *   The target is recomputed per pixel from the depth neighbourhood and never stored.  partials: the workspace of
+ *   mtgs_depth_normal_loss_workspace_floats floats (no initialisation).
+ * mtgs_depth_normal_loss_bwd: v_pred = v * (m sgn(pred - target) / (3 count) + the signs of the left/right and up/down
+ *   differences over their element counts), v = v_out[0]; `out` is the forward's (count = out[1]); sgn(0) = sgn(NaN) = 0
+ *   as in torch.abs's backward.
+ *   v = 0 writes exact zeros (a term that combine_losses dropped), also next to NaN pixels.
+ * mtgs_scale_reg_fwd: out[2] = {min(s, dim=1).mean(), mean(max(s_a / s_b, max_ratio) - max_ratio)} over scales [n, 3] fp32;
+ *   (s_a, s_b) = the largest and second-largest entry with two_d != 0 (torch.sort descending), (max, min) otherwise.  A row
+ *   with a NaN gives NaN in both terms; n = 0 gives NaN (mean of an empty tensor).  partials: mtgs_scale_reg_workspace_floats.
+ * mtgs_scale_reg_bwd: v_scales [n, 3] = the gradient of v_out[0] * out[0] + v_out[1] * out[1] (v_out: DEVICE [2]), by
+ *   PyTorch's backward rules:
+ *     - min(dim): the whole gradient v_out[0] / n goes to ONE entry, the lowest index among equal minima;
+ *     - two_d sort: s_a is the largest entry, lowest index on ties, s_b the largest of the other two, lowest index on ties
+ *       (the reference's order is unspecified there);
+ *     - two_d = 0: amax / amin split their gradient evenly among the entries equal to the max / min;
+ *     - maximum(ratio, max_ratio): the whole gradient when ratio > max_ratio (or NaN), half of it when equal, none below;
+ *     - the division: d/ds_a = g / s_b, d/ds_b = -g s_a / (s_b s_b).
+ *   A zero v_out[i] contributes exact zeros.
+ * Reductions: per-block partials, then a fixed-order fp64 sum; no float atomics (bitwise reproducible), no host reads and no
+ * allocation (graph-capturable).  The host checks name the bad argument (mtgs_rast_last_error). */
+int mtgs_depth_normals(int width, int height, const float *depth, const float *K, float *out, void *stream);
+int mtgs_depth_normal_loss_workspace_floats(int width, int height, size_t *n);
+int mtgs_depth_normal_loss_fwd(int width, int height, const float *pred, const float *depth, const float *K, const uint8_t *mask,
+                               float lo, float hi, int tv, float *partials, float *out, void *stream);
+int mtgs_depth_normal_loss_bwd(int width, int height, const float *pred, const float *depth, const float *K, const uint8_t *mask,
+                               float lo, float hi, int tv, const float *v_out, const float *out, float *v_pred, void *stream);
+int mtgs_scale_reg_workspace_floats(int64_t n, size_t *nf);
+int mtgs_scale_reg_fwd(int64_t n, const float *scales, int two_d, float max_ratio, float *partials, float *out, void *stream);
+int mtgs_scale_reg_bwd(int64_t n, const float *scales, int two_d, float max_ratio, const float *v_out, float *v_scales, void *stream);
+
 /* ---- SURVEY.md section 8f, rank 2 (second half): the optimizer step of every Gaussian parameter group in ONE launch ----
  * Reference: one torch.optim.Adam per parameter group with one tensor each (mtgs/scene_model/custom_trainer.py:115-136;
  * groups, learning rates and eps = 1e-15 in mtgs/config/MTGS.py:121-181); the densification moves the moments with their

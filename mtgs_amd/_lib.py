@@ -154,6 +154,13 @@ _SIGNATURES = {
     "mtgs_metrics_workspace_bytes": [_i64, _i32, C.POINTER(_sz)],
     "mtgs_color_correct": [_i64, _i32, C.c_double, _vp, _vp, _vp, _vp, _vp, _sz, _vp],
     "mtgs_image_metrics": [_i64, _i32, C.c_double, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _sz, _vp],
+    "mtgs_depth_normals": [_i32, _i32, _vp, _vp, _vp, _vp],
+    "mtgs_depth_normal_loss_workspace_floats": [_i32, _i32, C.POINTER(_sz)],
+    "mtgs_depth_normal_loss_fwd": [_i32, _i32, _vp, _vp, _vp, _vp, _f32, _f32, _i32, _vp, _vp, _vp],
+    "mtgs_depth_normal_loss_bwd": [_i32, _i32, _vp, _vp, _vp, _vp, _f32, _f32, _i32, _vp, _vp, _vp, _vp],
+    "mtgs_scale_reg_workspace_floats": [_i64, C.POINTER(_sz)],
+    "mtgs_scale_reg_fwd": [_i64, _vp, _i32, _f32, _vp, _vp, _vp],
+    "mtgs_scale_reg_bwd": [_i64, _vp, _i32, _f32, _vp, _vp, _vp],
     "mtgs_adam_group_bytes": [],
     "mtgs_adam_block_elems": [],
     "mtgs_adam_block_rows": [],

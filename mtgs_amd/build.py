@@ -25,8 +25,10 @@ COMMON_FLAGS = [
     f"--offload-arch={ARCH}", "-O3", "-std=c++17", "-fPIC", "-munsafe-fp-atomics", "-fno-slp-vectorize",
     "-Wall", "-Wno-unused-function", f"-I{PKG.parent / 'include'}",
 ]
-# The projection forward must round after every operation (bit-exact tile binning inputs).
-PER_FILE_FLAGS = {"project.hip": ["-ffp-contract=off"], "front.hip": ["-ffp-contract=off"], "metrics.hip": ["-ffp-contract=off"]}
+# The projection forward must round after every operation (bit-exact tile binning inputs); the metrics and the
+# geometric losses round as the reference's per-operation PyTorch kernels do.
+PER_FILE_FLAGS = {"project.hip": ["-ffp-contract=off"], "front.hip": ["-ffp-contract=off"], "metrics.hip": ["-ffp-contract=off"],
+                  "geomloss.hip": ["-ffp-contract=off"]}
 
 
 class HipccNotFound(RuntimeError):

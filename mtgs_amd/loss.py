@@ -418,3 +418,120 @@ def tv_loss(image: Tensor) -> Tensor:
     [H,W,C] (or [1,H,W,C]).  Two launches forward, one backward."""
     assert image.dim() in (3, 4) and (image.dim() == 3 or image.shape[0] == 1), image.shape
     return _TvLoss.apply(image)
+
+
+def _intrinsics(K: Tensor) -> Tensor:
+    """K [3,3] (or [1,3,3]) as the fp32 row-major device array the kernels read fx, fy, cx, cy from (no host read: a
+    float32 contiguous K is passed as it is, so a captured graph sees later writes into it)."""
+    assert K.numel() == 9, K.shape
+    return K.detach().to(torch.float32).reshape(3, 3).contiguous()
+
+
+def _depth_image(depth: Tensor) -> Tensor:
+    assert depth.dim() in (2, 3) and depth.numel() == depth.shape[0] * depth.shape[1], depth.shape
+    return depth.detach().to(torch.float32).reshape(depth.shape[0], depth.shape[1]).contiguous()
+
+
+def normals_from_depth(depth: Tensor, K: Tensor) -> Tensor:
+    """The target normal image of MTGS's depth-supervised normal loss and of its eval image
+    (mtgs/scene_model/mtgs_scene_graph.py:915-929, :1103-1121):
+        (1 + normal_from_depth_image(depth, fx, fy, cx, cy, (W, H), eye(4)) @ diag(1, -1, -1)) / 2
+    depth [H,W,1] / [H,W] (f16 is converted, as the reference's .float() does), K [3,3] intrinsics on the device (read by
+    the kernel: no .item()).  Returns [H,W,3] fp32; the one-pixel border is 0.5.  One launch, no gradient."""
+    assert K.numel() == 9, K.shape
+    require_gpu(depth, K)
+    d = _depth_image(depth)
+    k = _intrinsics(K)
+    H, W = d.shape
+    out = torch.empty((H, W, 3), dtype=torch.float32, device=d.device)
+    call("mtgs_depth_normals", W, H, ptr(d), ptr(k), ptr(out), stream_of(d))
+    return out
+
+
+class _DepthNormalLoss(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, pred, gt_depth, K, mask, lo, hi, tv):
+        require_gpu(pred, gt_depth, K, mask)
+        H, W = pred.shape[0], pred.shape[1]
+        p_c = pred.detach().to(torch.float32).contiguous()
+        d_c = _depth_image(gt_depth)
+        k_c = _intrinsics(K)
+        m_c = _mask_u8(mask, H, W)
+        n = C.c_size_t(0)
+        call("mtgs_depth_normal_loss_workspace_floats", W, H, C.byref(n))
+        partials = torch.empty(n.value, dtype=torch.float32, device=pred.device)
+        out = torch.empty(4, dtype=torch.float32, device=pred.device)
+        call("mtgs_depth_normal_loss_fwd", W, H, ptr(p_c), ptr(d_c), ptr(k_c), ptr(m_c), float(lo), float(hi), int(tv),
+             ptr(partials), ptr(out), stream_of(pred))
+        ctx.save_for_backward(p_c, d_c, k_c, m_c, out)
+        ctx.cfg = (H, W, float(lo), float(hi), int(tv), pred.dtype)
+        return out[0]
+
+    @staticmethod
+    def backward(ctx, v_out):
+        p_c, d_c, k_c, m_c, out = ctx.saved_tensors
+        H, W, lo, hi, tv, dtype = ctx.cfg
+        v = v_out.to(torch.float32).reshape(1).contiguous()
+        v_pred = torch.empty_like(p_c)
+        call("mtgs_depth_normal_loss_bwd", W, H, ptr(p_c), ptr(d_c), ptr(k_c), ptr(m_c), lo, hi, tv, ptr(v), ptr(out),
+             ptr(v_pred), stream_of(p_c))
+        return v_pred.to(dtype), None, None, None, None, None, None
+
+
+def depth_normal_loss(pred_normal: Tensor, gt_depth: Tensor, K: Tensor, mask: Optional[Tensor] = None, lo: float = 0.1,
+                      hi: float = 50.0, tv: bool = True) -> Tensor:
+    """MTGS's "Normal Loss" with normal_supervision = 'depth' (mtgs/scene_model/mtgs_scene_graph.py:905-935),
+    before normal_lambda:
+        m    = (gt_depth > lo) & (gt_depth < hi) & mask
+        loss = |normals_from_depth(gt_depth, K) - pred_normal|[m].mean() + (TVLoss()(pred_normal) if tv else 0)
+    pred_normal [H,W,3] (output_head's normal), gt_depth [H,W,1] / [H,W], K [3,3] on the device, mask [H,W,1] / [H,W] bool or
+    None.  The target is recomputed from the depth inside the kernels, never stored, and the intrinsics stay on the device,
+    so the term can be captured in a graph.  NaN when m is empty or pred_normal has NaN where it is read: pass it to
+    combine_losses(..., drop_if_not_finite=...) as the reference's `if torch.isfinite(normal_loss)` does.  Two launches
+    forward, one backward; differentiable with respect to pred_normal."""
+    assert pred_normal.dim() == 3 and pred_normal.shape[2] == 3, pred_normal.shape
+    H, W = pred_normal.shape[:2]
+    assert gt_depth.numel() == H * W and gt_depth.shape[0] == H and gt_depth.shape[1] == W, (pred_normal.shape, gt_depth.shape)
+    if mask is not None:
+        assert mask.numel() == H * W, mask.shape
+    assert K.numel() == 9, K.shape
+    if gt_depth.requires_grad:
+        raise NotImplementedError("depth_normal_loss: gradient with respect to gt_depth is not implemented")
+    return _DepthNormalLoss.apply(pred_normal, gt_depth, K, mask, lo, hi, bool(tv))
+
+
+class _ScaleRegularizers(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, scales, two_d, max_ratio):
+        require_gpu(scales)
+        s = scales.detach().to(torch.float32).contiguous()
+        N = s.shape[0]
+        n = C.c_size_t(0)
+        call("mtgs_scale_reg_workspace_floats", N, C.byref(n))
+        partials = torch.empty(n.value, dtype=torch.float32, device=s.device)
+        out = torch.empty(2, dtype=torch.float32, device=s.device)
+        call("mtgs_scale_reg_fwd", N, ptr(s), int(two_d), float(max_ratio), ptr(partials), ptr(out), stream_of(s))
+        ctx.save_for_backward(s)
+        ctx.cfg = (int(two_d), float(max_ratio), scales.dtype)
+        return out[0], out[1]
+
+    @staticmethod
+    def backward(ctx, v_two_d, v_sharp):
+        (s,) = ctx.saved_tensors
+        two_d, max_ratio, dtype = ctx.cfg
+        v = torch.stack([v_two_d.reshape(()), v_sharp.reshape(())]).to(torch.float32).contiguous()
+        v_s = torch.empty_like(s)
+        call("mtgs_scale_reg_bwd", s.shape[0], ptr(s), two_d, max_ratio, ptr(v), ptr(v_s), stream_of(s))
+        return v_s.to(dtype), None, None
+
+
+def scale_regularizers(scales: Tensor, two_d: bool = True, max_ratio: float = 10.0):
+    """MTGS's two regularisers on the collected scales (mtgs/scene_model/mtgs_scene_graph.py:936-940,
+    969-981), before sharp_shape_reg_lambda:
+        two_d_reg = torch.min(scales, dim=1, keepdim=True)[0].mean()
+        sharp_reg = mean(maximum(s_a / s_b, max_ratio) - max_ratio)
+    with (s_a, s_b) the two largest entries of each row when two_d (torch.sort descending), (amax, amin) otherwise.
+    scales [N,3] (the activated scales).  Returns (two_d_reg, sharp_reg) as 0-dim tensors; one pass each way for both.
+    Differentiable with respect to scales; the tie rules are documented in include/mtgs_rast.h."""
+    assert scales.dim() == 2 and scales.shape[1] == 3, scales.shape
+    return _ScaleRegularizers.apply(scales, bool(two_d), float(max_ratio))

@@ -31,7 +31,8 @@ import torch.nn.functional as F
 sys.path.insert(0, str(Path(__file__).resolve().parents[1]))
 from mtgs_amd import rasterization, spherical_harmonics  # noqa: E402
 from mtgs_amd.densify import update_statistics, update_statistics_all  # noqa: E402
-from mtgs_amd.loss import combine_losses, depth_ncc_loss, inverse_depth_l1, masked_l1, masked_ssim, output_head, tv_loss  # noqa: E402
+from mtgs_amd.loss import (combine_losses, depth_ncc_loss, depth_normal_loss, inverse_depth_l1, masked_l1, masked_ssim,  # noqa: E402
+                           output_head, scale_regularizers, tv_loss)
 from mtgs_amd.nodes import camera_space_normals, node_gaussians  # noqa: E402
 from mtgs_amd.synthetic import make_camera  # noqa: E402
 
@@ -172,6 +173,25 @@ def ncc_chain(pred_depth, gt_depth, patch_size=32, stride=16, mask=None):
     return 1 - ((pc / ps) * (gc / gs)).mean(dim=1).mean()
 
 
+def depth_normals_chain(depth, K):
+    """normal_from_depth_image -> @ diag(1,-1,-1) -> (1 + n) / 2 as MTGS runs it (mtgs_scene_graph.py:915-929; the intrinsics
+    read to the host, the back-projection through the inverse of an identity, pcd_to_normal's slices, cross, normalize, pad)"""
+    K = K.reshape(3, 3)
+    fx, fy, cx, cy = K[0, 0].item(), K[1, 1].item(), K[0, 2].item(), K[1, 2].item()
+    H, W = depth.shape[0], depth.shape[1]
+    d = depth.detach().float().reshape(-1)
+    uv = torch.stack(torch.meshgrid(torch.arange(W, device=d.device), torch.arange(H, device=d.device), indexing="xy"), -1)
+    uv = (uv + 0.5).view(-1, 2).float()
+    P = torch.stack([(uv[:, 0] - cx) * d / fx, (uv[:, 1] - cy) * d / fy, d], dim=-1)
+    c2w = torch.eye(4, device=d.device)
+    P = (P @ torch.linalg.inv(c2w[:3, :3]) + c2w[:3, 3]).view(H, W, 3)
+    a = P[1:-1, 2:] - P[1:-1, :-2]
+    b = P[:-2, 1:-1] - P[2:, 1:-1]
+    n = F.normalize(torch.cross(a, b, dim=-1), p=2, dim=-1)
+    n = F.pad(n.permute(2, 0, 1), (1, 1, 1, 1), mode="constant").permute(1, 2, 0)
+    return (1 + n @ torch.diag(n.new_tensor([1, -1, -1]))) / 2
+
+
 def _win(dev):
     c = torch.arange(11, dtype=torch.float) - 5
     g = torch.exp(-(c ** 2) / (2 * 1.5 ** 2))
@@ -204,6 +224,7 @@ LAZY = {"on": False}                     # --lazy-adam: exact lazy Adam for the 
 ALL_ROWS = {}                            # n -> int32 zeros [n]: a row map that selects every row (catch_up_rows)
 DPROWS = {"on": False}                   # --dp-rows: the sparse exchange hands ROWS to the optimizer (no dense gradient on any rank)
 REGS = {"on": False}                     # --regularizers: the 2D and sharp-shape terms on the collected scales
+GEOM = {"on": False}                     # --device-geometry-losses: the depth normal term and the regularisers on the device
 LAST = {"info": {}}                      # the device scalars of the last rasterization's `info` (graph mode: overflow flag and counts)
 
 
@@ -252,13 +273,19 @@ def iteration(P, cam, gt, mask, fused, stats, win, W, H, n=3, shipped=None):
         if fused:
             l1 = masked_l1(gt, app, mask)
             loss_d, dmask = inverse_depth_l1(depth, gt_d, mask, 0.1, 80.0, 1e-5)     # :849-858, 875-879: the mask is a by-product
-            loss_n = masked_l1(gt_n, normal, mask) + tv_loss(normal)                 # :931-934
+            if GEOM["on"]:      # normal_supervision = 'depth': the target from batch["depth"], the depth-range mask (:912-935)
+                loss_n = depth_normal_loss(normal, gt_d, K, mask, 0.1, 50.0, tv=True)
+            else:
+                loss_n = masked_l1(gt_n, normal, mask) + tv_loss(normal)                 # :931-934
         else:
             dmask = (gt_d > 0.1) & (gt_d < 80) & mask
             inv_gt, inv_pred = 1 / (gt_d + 1e-5), 1 / (depth + 1e-5)
             l1 = torch.abs(gt - app)[mask.squeeze(-1)].mean()
             loss_d = torch.abs(inv_gt - inv_pred)[dmask].mean()
-            loss_n = torch.abs(gt_n - normal)[mask.squeeze(-1)].mean() + \
+            nmask = mask.squeeze(-1)
+            if GEOM["on"]:
+                gt_n, nmask = depth_normals_chain(gt_d, K), ((gt_d > 0.1) & (gt_d < 50) & mask).squeeze(-1)
+            loss_n = torch.abs(gt_n - normal)[nmask].mean() + \
                 torch.mean(torch.abs(normal[:, :-1, :] - normal[:, 1:, :])) + torch.mean(torch.abs(normal[:-1, :, :] - normal[1:, :, :]))
         ssim = masked_ssim(gt, rgb, mask) if fused else ssim_chain(gt, rgb, mask, win)     # use_ssim_on_raw_rgb
         ncc = depth_ncc_loss(depth, gt_d, 32, 16, mask=dmask) if fused else ncc_chain(depth, gt_d, 32, 16, mask=dmask)   # :886-894
@@ -276,7 +303,10 @@ def iteration(P, cam, gt, mask, fused, stats, win, W, H, n=3, shipped=None):
         l1 = masked_l1(gt, rgb, mask) if fused else torch.abs(gt - rgb)[mask.squeeze(-1)].mean()
         ssim = masked_ssim(gt, rgb, mask) if fused else ssim_chain(gt, rgb, mask, win)
         loss = 0.8 * l1 + 0.2 * (1 - ssim)
-    if REGS["on"]:
+    if GEOM["on"] and fused:
+        two_d, sharp = scale_regularizers(gs["scales"], two_d=True, max_ratio=10.0)       # (one pass each way for both)
+        loss = loss + two_d + 1.0 * sharp
+    elif REGS["on"] or GEOM["on"]:
         # the terms of get_loss_dict that reach the Gaussians OUTSIDE the rasterization (mtgs_scene_graph.py:936-939, 969-981:
         # two_d_gaussians and sharp_shape_reg_lambda = 1.0 in config/MTGS.py:114-118): a dense gradient on the collected scales --
         # with --geometry-rows the optimizer steps scales with this .grad PLUS the rasterization's rows
@@ -865,6 +895,9 @@ def main():
                     "mtgs_node_bwd_rows, FusedAdam.set_row_gradient with one slice per rendered traversal; the colour tensors row-lazy)")
     ap.add_argument("--regularizers", action="store_true", help="add MTGS's '2D reg' and 'Sharp Shape Reg' terms on the collected scales "
                     "(mtgs_scene_graph.py:936-939, 969-981): loss terms that reach the Gaussians outside the rasterization")
+    ap.add_argument("--device-geometry-losses", action="store_true", help="with --shipped: MTGS's depth-supervised normal term "
+                    "(the target from each camera's gt_depth as batch['depth'], the depth-range mask) and the '2D reg' / 'Sharp Shape "
+                    "Reg' terms, on the device (mtgs_amd.loss.depth_normal_loss, scale_regularizers) in the fused iteration")
     ap.add_argument("--first-cap-scale", type=float, default=1.0, help="with --train-graph (tests): scale of the first graphs' capacities; "
                     "< 1 makes their frames overflow, which the loop must notice and repair")
     ap.add_argument("--steady", type=int, nargs=2, default=None, help="with --steps: also report the time per step between these two steps")
@@ -885,6 +918,11 @@ def main():
     VISFIRST["on"] = bool(args.visfirst)
     TOUCH["mode"], TOUCH["on"] = args.touch_first, args.touch_first == "on"
     REGS["on"] = bool(args.regularizers)
+    GEOM["on"] = bool(args.device_geometry_losses)
+    if GEOM["on"] and not args.shipped:
+        raise SystemExit("--device-geometry-losses needs --shipped (the normal term of the shipped option set)")
+    if GEOM["on"] and args.dp and args.dp_exchange == "sparse":
+        raise SystemExit("--device-geometry-losses: not with --dp-exchange sparse (its iteration keeps the precomputed target)")
     DPROWS["on"] = bool(args.dp_rows)
     if args.dp_rows and not (args.dp and args.dp_exchange == "sparse" and args.optimizer in (None, "fused")):
         raise SystemExit("--dp-rows needs --dp --dp-exchange sparse and the fused optimizer")

@@ -249,6 +249,14 @@ def call(name: str, *args) -> None:
         raise RuntimeError(f"{name} failed (code {rc}): {msg}")
 
 
+def workspace(name: str, *dims, device, dtype) -> torch.Tensor:
+    """The scratch tensor whose element count the size query `name` reports for `dims`: dtype torch.float32 for the
+    *_workspace_floats entry points, torch.uint8 for the *_workspace_bytes ones."""
+    n = C.c_size_t(0)
+    call(name, *dims, C.byref(n))
+    return torch.empty(n.value, dtype=dtype, device=device)
+
+
 def require_gpu(*tensors) -> None:
     for t in tensors:
         if t is not None and not t.is_cuda:

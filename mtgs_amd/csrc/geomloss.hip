@@ -19,6 +19,7 @@
 // No float atomics: every reduction is in a fixed order, so results are bitwise reproducible; nothing is read back to the
 // host and nothing is allocated here, so every entry point can be captured in a HIP graph.
 #include "common.hpp"
+#include "block_reduce.hpp"
 
 namespace {
 constexpr int GL_BLOCK = 256;
@@ -54,46 +55,11 @@ __device__ __forceinline__ float3 target_normal(int W, int H, int u, int v, cons
     return make_float3((1.f + f0) / 2.f, (1.f + f1) / 2.f, (1.f + f2) / 2.f);
 }
 
-// torch.abs's backward: grad * sgn(x) with sgn(0) = sgn(NaN) = 0
-__device__ __forceinline__ float sgn(float d) { return d > 0.f ? 1.f : (d < 0.f ? -1.f : 0.f); }
+// torch.abs's backward: grad * sgn(x) with sgn(0) = sgn(NaN) = 0  (tv.hip's sgn_nan keeps the NaN instead)
+__device__ __forceinline__ float sgn0(float d) { return d > 0.f ? 1.f : (d < 0.f ? -1.f : 0.f); }
 
 __device__ __forceinline__ bool selected(float d, int64_t p, const uint8_t *__restrict__ mask, float lo, float hi) {
     return d > lo && d < hi && (mask == nullptr || mask[p] != 0);
-}
-
-// Sum over the block (GL_BLOCK = 4 waves); every thread gets the total.
-__device__ __forceinline__ float block_sum(float v, float *lds) {
-    v = wave_sum_to_lane63(v);
-    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-    __syncthreads();
-    if (lane == 63) lds[wave] = v;
-    __syncthreads();
-    return (lds[0] + lds[1]) + (lds[2] + lds[3]);
-}
-
-// Fixed-order fp64 sum of K interleaved partials over nblocks blocks, by one block; thread 0 ends with the totals.
-template <int K>
-__device__ __forceinline__ void finish_sums(int64_t nblocks, const float *__restrict__ partials, double *s) {
-    __shared__ double lds[K][GL_BLOCK];
-    double acc[K];
-#pragma unroll
-    for (int j = 0; j < K; ++j) acc[j] = 0.0;
-    for (int64_t i = threadIdx.x; i < nblocks; i += GL_BLOCK) {
-#pragma unroll
-        for (int j = 0; j < K; ++j) acc[j] += (double)partials[i * K + j];
-    }
-#pragma unroll
-    for (int j = 0; j < K; ++j) lds[j][threadIdx.x] = acc[j];
-    __syncthreads();
-    for (int w = GL_BLOCK / 2; w > 0; w >>= 1) {
-        if ((int)threadIdx.x < w) {
-#pragma unroll
-            for (int j = 0; j < K; ++j) lds[j][threadIdx.x] += lds[j][threadIdx.x + w];
-        }
-        __syncthreads();
-    }
-#pragma unroll
-    for (int j = 0; j < K; ++j) s[j] = lds[j][0];
 }
 
 __global__ __launch_bounds__(GL_BLOCK) void depth_normals_kernel(int W, int H, const float *__restrict__ depth,
@@ -128,10 +94,10 @@ __global__ __launch_bounds__(GL_BLOCK) void normal_loss_fwd_kernel(int W, int H,
             }
         }
     }
-    l1 = block_sum(l1, s_red);
-    cnt = block_sum(cnt, s_red);
-    ta = block_sum(ta, s_red);
-    tb = block_sum(tb, s_red);
+    l1 = block_sum4(l1, s_red);
+    cnt = block_sum4(cnt, s_red);
+    ta = block_sum4(ta, s_red);
+    tb = block_sum4(tb, s_red);
     if (threadIdx.x == 0) {
         float *o = partials + (int64_t)blockIdx.x * NL_PARTS;
         o[0] = l1; o[1] = cnt; o[2] = ta; o[3] = tb;
@@ -142,7 +108,7 @@ __global__ __launch_bounds__(GL_BLOCK) void normal_loss_fwd_kernel(int W, int H,
 __global__ __launch_bounds__(GL_BLOCK) void normal_loss_finish_kernel(int64_t nblocks, double na, double nb, int tv,
                                                                       const float *__restrict__ partials, float *__restrict__ out) {
     double s[NL_PARTS];
-    finish_sums<NL_PARTS>(nblocks, partials, s);
+    finish_sums<NL_PARTS, GL_BLOCK>(nblocks, partials, s);
     if (threadIdx.x != 0) return;
     const float l1 = s[1] > 0.0 ? (float)(s[0] / (3.0 * s[1])) : __builtin_nanf("");
     float t = 0.f;
@@ -175,17 +141,17 @@ __global__ __launch_bounds__(GL_BLOCK) void normal_loss_bwd_kernel(int W, int H,
     if (selected(depth[p], p, mask, lo, hi)) {
         const float3 t = target_normal(W, H, u, r, depth, load_intr(K));
         const float w = v / (3.f * out[1]);          // mean's backward: v / numel of the selection
-        g[0] = w * sgn(q[0] - t.x); g[1] = w * sgn(q[1] - t.y); g[2] = w * sgn(q[2] - t.z);
+        g[0] = w * sgn0(q[0] - t.x); g[1] = w * sgn0(q[1] - t.y); g[2] = w * sgn0(q[2] - t.z);
     }
     if (tv) {
         const float va = v * inv_a, vb = v * inv_b;
 #pragma unroll
         for (int c = 0; c < 3; ++c) {
             float ga = 0.f, gb = 0.f;
-            if (u + 1 < W) ga += sgn(q[c] - pred[p * 3 + 3 + c]);
-            if (u > 0) ga -= sgn(pred[p * 3 - 3 + c] - q[c]);
-            if (r + 1 < H) gb += sgn(q[c] - pred[(p + W) * 3 + c]);
-            if (r > 0) gb -= sgn(pred[(p - W) * 3 + c] - q[c]);
+            if (u + 1 < W) ga += sgn0(q[c] - pred[p * 3 + 3 + c]);
+            if (u > 0) ga -= sgn0(pred[p * 3 - 3 + c] - q[c]);
+            if (r + 1 < H) gb += sgn0(q[c] - pred[(p + W) * 3 + c]);
+            if (r > 0) gb -= sgn0(pred[(p - W) * 3 + c] - q[c]);
             if (W > 1) g[c] += va * ga;              // (an empty difference image: no gradient, as torch's empty mean)
             if (H > 1) g[c] += vb * gb;
         }
@@ -237,15 +203,15 @@ __global__ __launch_bounds__(GL_BLOCK) void scale_reg_fwd_kernel(int64_t n, cons
             b = (r.ratio > max_ratio ? r.ratio : max_ratio) - max_ratio;
         }
     }
-    a = block_sum(a, s_red);
-    b = block_sum(b, s_red);
+    a = block_sum4(a, s_red);
+    b = block_sum4(b, s_red);
     if (threadIdx.x == 0) { partials[(int64_t)blockIdx.x * SR_PARTS] = a; partials[(int64_t)blockIdx.x * SR_PARTS + 1] = b; }
 }
 
 __global__ __launch_bounds__(GL_BLOCK) void scale_reg_finish_kernel(int64_t nblocks, int64_t n, const float *__restrict__ partials,
                                                                     float *__restrict__ out) {
     double s[SR_PARTS];
-    finish_sums<SR_PARTS>(nblocks, partials, s);
+    finish_sums<SR_PARTS, GL_BLOCK>(nblocks, partials, s);
     if (threadIdx.x != 0) return;
     out[0] = n > 0 ? (float)(s[0] / (double)n) : __builtin_nanf("");
     out[1] = n > 0 ? (float)(s[1] / (double)n) : __builtin_nanf("");

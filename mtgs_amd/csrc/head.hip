@@ -13,6 +13,7 @@
 // nothing arrived) and v_alpha once, and reduces the gradients of the background (3) and of E (12) through per-block
 // partial sums in a fixed order.  Roofline: HBM (image-sized streams).
 #include "common.hpp"
+#include "block_reduce.hpp"
 
 namespace {
 constexpr int HEAD_BLOCK = 256, HEAD_RED = 15;   // 3 background + 12 exposure partial sums per block
@@ -47,15 +48,6 @@ __global__ __launch_bounds__(HEAD_BLOCK) void head_fwd_kernel(int64_t P, HeadCfg
         const float inv = 1.0f / sqrtf((nx * nx + ny * ny) + nz * nz);   // no epsilon in the reference: 0/0 = NaN where nothing was hit
         normal[p * 3] = (nx * inv + 1.f) * 0.5f; normal[p * 3 + 1] = (ny * inv + 1.f) * 0.5f; normal[p * 3 + 2] = (nz * inv + 1.f) * 0.5f;
     }
-}
-
-__device__ __forceinline__ float block_sum(float v, float *lds) {
-    v = wave_sum_to_lane63(v);
-    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-    __syncthreads();
-    if (lane == 63) lds[wave] = v;
-    __syncthreads();
-    return (lds[0] + lds[1]) + (lds[2] + lds[3]);
 }
 
 __global__ __launch_bounds__(HEAD_BLOCK) void head_bwd_kernel(int64_t P, HeadCfg cfg, const float *__restrict__ render,
@@ -110,7 +102,7 @@ __global__ __launch_bounds__(HEAD_BLOCK) void head_bwd_kernel(int64_t P, HeadCfg
     }
 #pragma unroll
     for (int k = 0; k < HEAD_RED; ++k) {
-        const float s = block_sum(red[k], s_red);
+        const float s = block_sum4(red[k], s_red);
         if (threadIdx.x == 0) partials[(int64_t)blockIdx.x * HEAD_RED + k] = s;
     }
 }
@@ -122,7 +114,7 @@ __global__ __launch_bounds__(HEAD_BLOCK) void head_finish_kernel(int64_t nblocks
     const int k = blockIdx.x;      // one workgroup per column (15 columns one after the other in ONE workgroup: 19 us of latency)
     float s = 0.f;
     for (int64_t b = threadIdx.x; b < nblocks; b += HEAD_BLOCK) s += partials[b * HEAD_RED + k];
-    const float tot = block_sum(s, s_red);
+    const float tot = block_sum4(s, s_red);
     if (threadIdx.x == 0) {
         if (k < 3) { if (v_bg) v_bg[k] = tot; }
         else if (v_E) v_E[k - 3] = tot;

@@ -15,20 +15,12 @@
 //
 // Roofline: HBM (forward reads 2 x 12 B per pixel and writes 36 B of gradient maps; backward reads 36 + 24, writes 12).
 #include "common.hpp"
+#include "block_reduce.hpp"
 
 namespace {
 
 constexpr int WIN = 11, HALO = WIN - 1, TILE = 16, IN_TILE = TILE + HALO;  // 26
 struct Window { float w[WIN]; };
-
-__device__ __forceinline__ float block_sum_256(float v, float *lds) {
-    v = wave_sum_to_lane63(v);
-    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-    __syncthreads();
-    if (lane == 63) lds[wave] = v;
-    __syncthreads();
-    return (lds[0] + lds[1]) + (lds[2] + lds[3]);
-}
 
 // gmaps[(oy * OW + ox) * 9 + c * 3 + {0,1,2}] = mask * d ssim / d {mu_y, E[y^2], E[xy]}   (nullable)
 __global__ __launch_bounds__(256) void ssim_fwd_kernel(int H, int W, const float *__restrict__ X, const float *__restrict__ Y,
@@ -110,8 +102,8 @@ __global__ __launch_bounds__(256) void ssim_fwd_kernel(int H, int W, const float
             g[0] = g_mu; g[1] = g_e22; g[2] = g_e12;
         }
     }
-    const float bs = block_sum_256(sum, s_red);
-    const float bc = block_sum_256(3.f * m, s_red);
+    const float bs = block_sum4(sum, s_red);
+    const float bc = block_sum4(3.f * m, s_red);
     if (tid == 0) {
         const int64_t b = (int64_t)blockIdx.y * gridDim.x + blockIdx.x;
         partials[b * 2] = bs; partials[b * 2 + 1] = bc;
@@ -124,8 +116,8 @@ __global__ __launch_bounds__(256) void ssim_finish_kernel(int64_t nblocks, const
     __shared__ float s_red[4];
     float s = 0.f, c = 0.f;
     for (int64_t b = threadIdx.x; b < nblocks; b += 256) { s += partials[b * 2]; c += partials[b * 2 + 1]; }
-    const float ts = block_sum_256(s, s_red);
-    const float tc = block_sum_256(c, s_red);
+    const float ts = block_sum4(s, s_red);
+    const float tc = block_sum4(c, s_red);
     if (threadIdx.x == 0) { out[0] = ts / tc; out[1] = tc; }
 }
 
@@ -135,8 +127,8 @@ __global__ __launch_bounds__(256) void mean_or_zero_finish_kernel(int64_t nblock
     __shared__ float s_red[4];
     float s = 0.f, c = 0.f;
     for (int64_t b = threadIdx.x; b < nblocks; b += 256) { s += partials[b * 2]; c += partials[b * 2 + 1]; }
-    const float ts = block_sum_256(s, s_red);
-    const float tc = block_sum_256(c, s_red);
+    const float ts = block_sum4(s, s_red);
+    const float tc = block_sum4(c, s_red);
     if (threadIdx.x == 0) { out[0] = tc > 0.f ? ts / tc : 0.f; out[1] = tc; }
 }
 
@@ -229,8 +221,8 @@ __global__ __launch_bounds__(256) void l1_fwd_kernel(int64_t n_pix, int ch, cons
             c += (float)ch;
         }
     }
-    const float bs = block_sum_256(s, s_red);
-    const float bc = block_sum_256(c, s_red);
+    const float bs = block_sum4(s, s_red);
+    const float bc = block_sum4(c, s_red);
     if (threadIdx.x == 0) { partials[blockIdx.x * 2] = bs; partials[blockIdx.x * 2 + 1] = bc; }
 }
 __global__ __launch_bounds__(256) void l1_bwd_kernel(int64_t n_pix, int ch, const float *__restrict__ X, const float *__restrict__ Y,
@@ -264,8 +256,8 @@ __global__ __launch_bounds__(256) void inv_depth_l1_fwd_kernel(int64_t n_pix, co
         if (mask_out) mask_out[p] = m ? 1 : 0;
         if (m) { s += fabsf(1.0f / (g + eps) - 1.0f / (pred[p] + eps)); c += 1.f; }
     }
-    const float bs = block_sum_256(s, s_red);
-    const float bc = block_sum_256(c, s_red);
+    const float bs = block_sum4(s, s_red);
+    const float bc = block_sum4(c, s_red);
     if (threadIdx.x == 0) { partials[blockIdx.x * 2] = bs; partials[blockIdx.x * 2 + 1] = bc; }
 }
 // d/d pred of |a - 1 / (pred + eps)| = sign(1 / (pred + eps) - a) * (-1 / (pred + eps)^2); torch's chain: grad of abs = sign(.),

@@ -11,6 +11,7 @@
 // image, ref and mask (25 B per pixel) and writes nothing per pixel but the final output.  No float atomics and no host reads:
 // the result is bitwise reproducible and the call can be captured in a graph.  DESIGN.md section 9.
 #include "common.hpp"
+#include "block_reduce.hpp"
 
 namespace {
 
@@ -151,13 +152,8 @@ __global__ __launch_bounds__(RB) void metrics_reduce_kernel(int nb, const double
     const int e = blockIdx.x, tid = threadIdx.x;
     double a = 0.0;
     for (int b = tid; b < nb; b += RB) a += part[(int64_t)e * nb + b];
-    s[tid] = a;
-    __syncthreads();
-    for (int o = RB / 2; o > 0; o >>= 1) {
-        if (tid < o) s[tid] += s[tid + o];
-        __syncthreads();
-    }
-    if (tid == 0) total[e] = s[0];
+    const double t = block_tree_sum_f64<RB>(a, s);
+    if (tid == 0) total[e] = t;
 }
 
 // Thread c < 3 solves (A^T M A) w = A^T M b of channel c by an fp64 Cholesky factorisation, writes W_k[c] and ORs a failure

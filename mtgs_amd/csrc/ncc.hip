@@ -11,20 +11,12 @@
 // one-pass variance cancels catastrophically on flat depth), per-patch statistics saved.  Backward: thread per PIXEL,
 // gathering from the <= (k / stride)^2 patches that contain it (no atomics, no zero-fill).  Roofline: latency / L2.
 #include "common.hpp"
+#include "block_reduce.hpp"
 
 namespace {
 constexpr int NCC_BLOCK = 256, NCC_STATS = 6;   // pm, gm, ps, gs, C = mean(pc gc), valid
 
 struct NccGrid { int H, W, k, s, pad, Lh, Lw; };
-
-__device__ __forceinline__ float block_sum(float v, float *lds) {
-    v = wave_sum_to_lane63(v);
-    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-    __syncthreads();
-    if (lane == 63) lds[wave] = v;
-    __syncthreads();
-    return (lds[0] + lds[1]) + (lds[2] + lds[3]);
-}
 
 __global__ __launch_bounds__(NCC_BLOCK) void ncc_fwd_kernel(NccGrid G, const float *__restrict__ pred, const float *__restrict__ gt,
                                                             const uint8_t *__restrict__ mask, float *__restrict__ stats) {
@@ -41,20 +33,20 @@ __global__ __launch_bounds__(NCC_BLOCK) void ncc_fwd_kernel(NccGrid G, const flo
             sp += pred[q]; sg += gt[q];
         }
     }
-    const float nbad = block_sum(bad, s_red);
+    const float nbad = block_sum4(bad, s_red);
     if (!inside || nbad > 0.f) {
         if (threadIdx.x == 0) { st[0] = st[1] = st[4] = 0.f; st[2] = st[3] = 1.f; st[5] = 0.f; }
         return;
     }
     const float inv_n = 1.0f / (float)n;
-    const float pm = block_sum(sp, s_red) * inv_n, gm = block_sum(sg, s_red) * inv_n;
+    const float pm = block_sum4(sp, s_red) * inv_n, gm = block_sum4(sg, s_red) * inv_n;
     float spp = 0.f, sgg = 0.f, spg = 0.f;
     for (int e = threadIdx.x; e < n; e += NCC_BLOCK) {
         const int64_t q = (int64_t)(y0 + e / G.k) * G.W + x0 + e % G.k;
         const float pc = pred[q] - pm, gc = gt[q] - gm;
         spp += pc * pc; sgg += gc * gc; spg += pc * gc;
     }
-    const float vp = block_sum(spp, s_red) * inv_n, vg = block_sum(sgg, s_red) * inv_n, c = block_sum(spg, s_red) * inv_n;
+    const float vp = block_sum4(spp, s_red) * inv_n, vg = block_sum4(sgg, s_red) * inv_n, c = block_sum4(spg, s_red) * inv_n;
     if (threadIdx.x == 0) {
         st[0] = pm; st[1] = gm; st[2] = sqrtf(vp + 1e-8f); st[3] = sqrtf(vg + 1e-8f); st[4] = c; st[5] = 1.f;
     }
@@ -69,7 +61,7 @@ __global__ __launch_bounds__(NCC_BLOCK) void ncc_finish_kernel(int64_t L, const 
         const float *st = stats + p * NCC_STATS;
         if (st[5] != 0.f) { s += st[4] / (st[2] * st[3]); c += 1.f; }
     }
-    const float ts = block_sum(s, s_red), tc = block_sum(c, s_red);
+    const float ts = block_sum4(s, s_red), tc = block_sum4(c, s_red);
     if (threadIdx.x == 0) { out[0] = 1.f - ts / tc; out[1] = tc; }
 }
 

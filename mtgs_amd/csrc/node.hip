@@ -24,20 +24,6 @@
 
 namespace {
 
-// The addend must be a ROUNDED product (mul_rounded at the call sites; HIP's __fmul_rn is a plain, contractable `*`): if the compiler contracts the multiply into the
-// first add, lane L gets fma(b_L, c_L, round(b_M c_M)) and its partner M the mirror image -- 1 ulp apart, which made a
-// Gaussian's colour depend on its position in the wave (tests/test_gpu_large.py renders a subset bit-identically).
-__device__ __forceinline__ float mul_rounded(float a, float b) {
-#pragma clang fp contract(off)
-    return a * b;
-}
-__device__ __forceinline__ float row16_sum(float v) {  // sum over the 16 lanes of a DPP row, in every lane
-    v += dpp_mov<0xB1>(v);   // quad_perm [1,0,3,2]
-    v += dpp_mov<0x4E>(v);   // quad_perm [2,3,0,1]
-    v += dpp_mov<0x141>(v);  // row_half_mirror
-    v += dpp_mov<0x140>(v);  // row_mirror
-    return v;
-}
 __device__ __forceinline__ float quad_sum(float v) {   // sum over the 4 lanes of a quad, in every lane
     v += dpp_mov<0xB1>(v);
     v += dpp_mov<0x4E>(v);

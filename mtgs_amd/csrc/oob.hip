@@ -10,6 +10,7 @@
 //     loss = loss / count   (only when count != 0)
 // Table of descriptors in device memory as for the node activations (include/mtgs_rast.h: mtgs_oob_desc).
 #include "common.hpp"
+#include "block_reduce.hpp"
 
 namespace {
 constexpr int OOB_BLOCK = 256;
@@ -39,15 +40,6 @@ __device__ __forceinline__ bool is_oob(const mtgs_oob_desc &d, int64_t i) {
     return fabsf(x) > d.limit[0] || fabsf(y) > d.limit[1] || fabsf(z) > d.limit[2];
 }
 
-__device__ __forceinline__ float block_sum(float v, float *lds) {
-    v = wave_sum_to_lane63(v);
-    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-    __syncthreads();
-    if (lane == 63) lds[wave] = v;
-    __syncthreads();
-    return (lds[0] + lds[1]) + (lds[2] + lds[3]);
-}
-
 __global__ __launch_bounds__(OOB_BLOCK) void oob_fwd_kernel(const mtgs_oob_desc *__restrict__ table, int n_nodes,
                                                             const int32_t *__restrict__ flags, float *__restrict__ partials) {
     __shared__ float s_red[4];
@@ -60,7 +52,7 @@ __global__ __launch_bounds__(OOB_BLOCK) void oob_fwd_kernel(const mtgs_oob_desc 
         term = -logf((1.f - s) + 1e-6f);
         cnt = 1.f;
     }
-    const float bs = block_sum(term, s_red), bc = block_sum(cnt, s_red);
+    const float bs = block_sum4(term, s_red), bc = block_sum4(cnt, s_red);
     if (threadIdx.x == 0) { partials[(int64_t)blockIdx.x * 2] = bs; partials[(int64_t)blockIdx.x * 2 + 1] = bc; }
 }
 
@@ -70,7 +62,7 @@ __global__ __launch_bounds__(OOB_BLOCK) void oob_finish_kernel(int64_t nblocks, 
     __shared__ float s_red[4];
     float s = 0.f, c = 0.f;
     for (int64_t b = threadIdx.x; b < nblocks; b += OOB_BLOCK) { s += partials[b * 2]; c += partials[b * 2 + 1]; }
-    const float ts = block_sum(s, s_red), tc = block_sum(c, s_red);
+    const float ts = block_sum4(s, s_red), tc = block_sum4(c, s_red);
     if (threadIdx.x == 0) { out[0] = tc > 0.f ? ts / tc : 0.f; out[1] = tc; }
 }
 

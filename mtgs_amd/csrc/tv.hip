@@ -7,18 +7,10 @@
 // Forward: per-block partial sums of both terms in a fixed order; backward: thread per element gathering the signs of
 // its (up to) four differences.  NaN inputs propagate as in the reference (MTGS drops the term when it is not finite).
 #include "common.hpp"
+#include "block_reduce.hpp"
 
 namespace {
 constexpr int TV_BLOCK = 256;
-
-__device__ __forceinline__ float block_sum(float v, float *lds) {
-    v = wave_sum_to_lane63(v);
-    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-    __syncthreads();
-    if (lane == 63) lds[wave] = v;
-    __syncthreads();
-    return (lds[0] + lds[1]) + (lds[2] + lds[3]);
-}
 
 __global__ __launch_bounds__(TV_BLOCK) void tv_fwd_kernel(int H, int W, int C, const float *__restrict__ x, float *__restrict__ partials) {
     __shared__ float s_red[4];
@@ -31,7 +23,7 @@ __global__ __launch_bounds__(TV_BLOCK) void tv_fwd_kernel(int H, int W, int C, c
         if (col + 1 < W) a = fabsf(v - x[e + C]);
         if (row + 1 < H) b = fabsf(v - x[e + (int64_t)W * C]);
     }
-    const float sa = block_sum(a, s_red), sb = block_sum(b, s_red);
+    const float sa = block_sum4(a, s_red), sb = block_sum4(b, s_red);
     if (threadIdx.x == 0) { partials[(int64_t)blockIdx.x * 2] = sa; partials[(int64_t)blockIdx.x * 2 + 1] = sb; }
 }
 
@@ -40,11 +32,11 @@ __global__ __launch_bounds__(TV_BLOCK) void tv_finish_kernel(int64_t nblocks, fl
     __shared__ float s_red[4];
     float a = 0.f, b = 0.f;
     for (int64_t i = threadIdx.x; i < nblocks; i += TV_BLOCK) { a += partials[i * 2]; b += partials[i * 2 + 1]; }
-    const float ta = block_sum(a, s_red), tb = block_sum(b, s_red);
+    const float ta = block_sum4(a, s_red), tb = block_sum4(b, s_red);
     if (threadIdx.x == 0) out[0] = ta * inv_a + tb * inv_b;
 }
 
-__device__ __forceinline__ float sgn(float d) { return d > 0.f ? 1.f : (d < 0.f ? -1.f : (d == 0.f ? 0.f : d)); }   // NaN stays NaN
+__device__ __forceinline__ float sgn_nan(float d) { return d > 0.f ? 1.f : (d < 0.f ? -1.f : (d == 0.f ? 0.f : d)); }   // NaN stays NaN (geomloss.hip's sgn0 drops it)
 
 __global__ __launch_bounds__(TV_BLOCK) void tv_bwd_kernel(int H, int W, int C, const float *__restrict__ x, const float *__restrict__ v_out,
                                                           float inv_a, float inv_b, float *__restrict__ v_x) {
@@ -54,10 +46,10 @@ __global__ __launch_bounds__(TV_BLOCK) void tv_bwd_kernel(int H, int W, int C, c
     const int col = (int)(pix % W), row = (int)(pix / W);
     const float v = x[e];
     float ga = 0.f, gb = 0.f;
-    if (col + 1 < W) ga += sgn(v - x[e + C]);
-    if (col > 0) ga -= sgn(x[e - C] - v);
-    if (row + 1 < H) gb += sgn(v - x[e + rs]);
-    if (row > 0) gb -= sgn(x[e - rs] - v);
+    if (col + 1 < W) ga += sgn_nan(v - x[e + C]);
+    if (col > 0) ga -= sgn_nan(x[e - C] - v);
+    if (row + 1 < H) gb += sgn_nan(v - x[e + rs]);
+    if (row > 0) gb -= sgn_nan(x[e - rs] - v);
     v_x[e] = v_out[0] == 0.f ? 0.f : v_out[0] * (ga * inv_a + gb * inv_b);   // zero cotangent -> zero, also next to NaN pixels
 }
 

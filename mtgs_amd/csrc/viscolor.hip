@@ -19,17 +19,6 @@ namespace {
 
 constexpr int VC_BLOCK = 256, VC_ROWS_PER_BLOCK = VC_BLOCK / 16;
 
-__device__ __forceinline__ float mul_rounded(float a, float b) {   // (see node.hip: keeps the colour independent of the lane)
-#pragma clang fp contract(off)
-    return a * b;
-}
-__device__ __forceinline__ float row16_sum(float v) {
-    v += dpp_mov<0xB1>(v);
-    v += dpp_mov<0x4E>(v);
-    v += dpp_mov<0x141>(v);
-    v += dpp_mov<0x140>(v);
-    return v;
-}
 struct F3 { float x, y, z; };
 // (non-temporal, as sh_fwd_k16_kernel's: the coefficient rows are read once per frame and would only push the records and gradient
 //  rows of this frame out of the Infinity Cache -- 46.7 -> 41.6 us for the call at the headline workload, with 64 instead of 128

@@ -9,7 +9,7 @@
 // Result layout: out[i], row r (lanes 16r..16r+15, every lane of the row) = sum over the wave of
 // in[4*i + r].
 #pragma once
-#include <hip/hip_runtime.h>
+#include "common.hpp"
 
 // The clang builtins __builtin_amdgcn_permlane{16,32}_swap of ROCm 7.2 return the first result in
 // both vector elements, so the instructions are issued directly.  The s_nop covers the VALU-write ->
@@ -19,11 +19,6 @@ __device__ __forceinline__ void permlane16_swap(float &a, float &b) {
 }
 __device__ __forceinline__ void permlane32_swap(float &a, float &b) {
     asm volatile("s_nop 1\n\tv_permlane32_swap_b32 %0, %1" : "+v"(a), "+v"(b));
-}
-
-template <int CTRL>
-__device__ __forceinline__ float dpp_perm(float v) {
-    return __builtin_bit_cast(float, __builtin_amdgcn_update_dpp(0, __builtin_bit_cast(int, v), CTRL, 0xf, 0xf, true));
 }
 
 // in: 4*NR values per lane (clobbered).  out[NR] as described above.
@@ -40,10 +35,10 @@ __device__ __forceinline__ void wave_reduce_x4(float *in, float *out) {
         // [a01,b01,a23,b23] x [c01,d01,c23,d23] -> [a, b, c, d] partial sums, one value per row
         permlane32_swap(a, c);
         a += c;
-        a += dpp_perm<0xB1>(a);   // quad_perm [1,0,3,2]
-        a += dpp_perm<0x4E>(a);   // quad_perm [2,3,0,1]
-        a += dpp_perm<0x141>(a);  // row_half_mirror
-        a += dpp_perm<0x140>(a);  // row_mirror
+        a += dpp_mov<0xB1>(a);   // quad_perm [1,0,3,2]
+        a += dpp_mov<0x4E>(a);   // quad_perm [2,3,0,1]
+        a += dpp_mov<0x141>(a);  // row_half_mirror
+        a += dpp_mov<0x140>(a);  // row_mirror
         out[i] = a;
     }
 }
@@ -86,19 +81,19 @@ __device__ __forceinline__ float wave_reduce_x4_packed(float *in) {
         reg[i] = a + c;
     }
     // level 1: halves of a row
-    float w01 = reg[0] + dpp_perm<0x128>(reg[0]);   // row_ror:8 -> lanes i and i^8 summed, in every lane
+    float w01 = reg[0] + dpp_mov<0x128>(reg[0]);   // row_ror:8 -> lanes i and i^8 summed, in every lane
     row_pair(w01, reg[1]);                          // lanes 8-15 <- register 1
     float w23;
     if (NR == 4) {
-        w23 = reg[2] + dpp_perm<0x128>(reg[2]);
+        w23 = reg[2] + dpp_mov<0x128>(reg[2]);
         row_pair(w23, reg[3]);
     } else {
-        w23 = reg[2] + dpp_perm<0x128>(reg[2]);     // both halves hold register 2
+        w23 = reg[2] + dpp_mov<0x128>(reg[2]);     // both halves hold register 2
     }
     // level 2: quads
-    float v = w01 + dpp_perm<0x141>(w01);           // row_half_mirror: the 4 distinct pair sums of a half, twice
+    float v = w01 + dpp_mov<0x141>(w01);           // row_half_mirror: the 4 distinct pair sums of a half, twice
     quad_pair(v, w23);                              // quads 1 and 3 <- registers 2 / 3
-    v += dpp_perm<0xB1>(v);                         // quad_perm [1,0,3,2]
-    v += dpp_perm<0x4E>(v);                         // quad_perm [2,3,0,1]
+    v += dpp_mov<0xB1>(v);                         // quad_perm [1,0,3,2]
+    v += dpp_mov<0x4E>(v);                         // quad_perm [2,3,0,1]
     return v;
 }

@@ -15,7 +15,7 @@ import numpy as np
 import torch
 from torch import Tensor
 
-from ._lib import call, ptr, require_gpu, stream_of
+from ._lib import call, ptr, require_gpu, stream_of, workspace
 
 
 def _mask_u8(mask: Optional[Tensor], H: int, W: int) -> Optional[Tensor]:
@@ -27,18 +27,27 @@ def _mask_u8(mask: Optional[Tensor], H: int, W: int) -> Optional[Tensor]:
     return m.view(torch.uint8) if m.dtype == torch.bool else m.to(torch.uint8)
 
 
+def _as_f32(t: Tensor, *shape) -> Tensor:
+    """The detached fp32 contiguous array (reshaped to `shape` when given) a kernel reads: no copy when `t` already is one."""
+    t = t.detach().to(torch.float32)
+    return (t.reshape(shape) if shape else t).contiguous()
+
+
+def _cotangent(v_out: Tensor) -> Tensor:
+    """The cotangent of a scalar loss as the one-element fp32 device array the backward kernels read."""
+    return v_out.to(torch.float32).reshape(1).contiguous()
+
+
 class _MaskedSSIM(torch.autograd.Function):
     @staticmethod
     def forward(ctx, gt, pred, mask, win_sigma, data_range, K1, K2):
         require_gpu(gt, pred, mask)
         H, W = pred.shape[:2]
-        gt_c = gt.detach().to(torch.float32).contiguous()
-        pred_c = pred.detach().to(torch.float32).contiguous()
+        gt_c = _as_f32(gt)
+        pred_c = _as_f32(pred)
         mask_c = _mask_u8(mask, H, W)
         dev = pred.device
-        n = C.c_size_t(0)
-        call("mtgs_ssim_workspace_floats", W, H, C.byref(n))
-        partials = torch.empty(n.value, dtype=torch.float32, device=dev)
+        partials = workspace("mtgs_ssim_workspace_floats", W, H, device=dev, dtype=torch.float32)
         out = torch.empty(2, dtype=torch.float32, device=dev)
         need = ctx.needs_input_grad[1]
         gmaps = torch.empty(((H - 10), (W - 10), 9), dtype=torch.float32, device=dev) if need else None
@@ -52,7 +61,7 @@ class _MaskedSSIM(torch.autograd.Function):
     def backward(ctx, v_out):
         gt_c, pred_c, gmaps, out = ctx.saved_tensors
         H, W, win_sigma, dtype = ctx.dims
-        v = v_out.to(torch.float32).reshape(1).contiguous()
+        v = _cotangent(v_out)
         v_pred = torch.empty_like(pred_c)
         call("mtgs_ssim_bwd", W, H, ptr(gt_c), ptr(pred_c), ptr(gmaps), win_sigma, ptr(v), ptr(out), ptr(v_pred),
              stream_of(pred_c))
@@ -80,12 +89,10 @@ class _MaskedL1(torch.autograd.Function):
     def forward(ctx, gt, pred, mask):
         require_gpu(gt, pred, mask)
         H, W = pred.shape[:2]
-        gt_c = gt.detach().to(torch.float32).contiguous()
-        pred_c = pred.detach().to(torch.float32).contiguous()
+        gt_c = _as_f32(gt)
+        pred_c = _as_f32(pred)
         mask_c = _mask_u8(mask, H, W)
-        n = C.c_size_t(0)
-        call("mtgs_l1_workspace_floats", W, H, C.byref(n))
-        partials = torch.empty(n.value, dtype=torch.float32, device=pred.device)
+        partials = workspace("mtgs_l1_workspace_floats", W, H, device=pred.device, dtype=torch.float32)
         out = torch.empty(2, dtype=torch.float32, device=pred.device)
         ch = pred.shape[2]
         call("mtgs_l1_fwd", W, H, ch, ptr(gt_c), ptr(pred_c), ptr(mask_c), ptr(partials), ptr(out), stream_of(pred))
@@ -97,7 +104,7 @@ class _MaskedL1(torch.autograd.Function):
     def backward(ctx, v_out):
         gt_c, pred_c, mask_c, out = ctx.saved_tensors
         H, W, ch, dtype = ctx.dims
-        v = v_out.to(torch.float32).reshape(1).contiguous()
+        v = _cotangent(v_out)
         v_pred = torch.empty_like(pred_c)
         call("mtgs_l1_bwd", W, H, ch, ptr(gt_c), ptr(pred_c), ptr(mask_c), ptr(v), ptr(out), ptr(v_pred), stream_of(pred_c))
         return None, v_pred.to(dtype), None
@@ -122,12 +129,10 @@ class _InverseDepthL1(torch.autograd.Function):
     def forward(ctx, gt_depth, depth, mask, lo, hi, eps):
         require_gpu(gt_depth, depth, mask)
         H, W = depth.shape[:2]
-        gt_c = gt_depth.detach().to(torch.float32).reshape(H, W).contiguous()
-        d_c = depth.detach().to(torch.float32).reshape(H, W).contiguous()
+        gt_c = _as_f32(gt_depth, H, W)
+        d_c = _as_f32(depth, H, W)
         mask_c = _mask_u8(mask, H, W)
-        n = C.c_size_t(0)
-        call("mtgs_l1_workspace_floats", W, H, C.byref(n))
-        partials = torch.empty(n.value, dtype=torch.float32, device=depth.device)
+        partials = workspace("mtgs_l1_workspace_floats", W, H, device=depth.device, dtype=torch.float32)
         out = torch.empty(2, dtype=torch.float32, device=depth.device)
         used = torch.empty((H, W), dtype=torch.uint8, device=depth.device)
         call("mtgs_inv_depth_l1_fwd", W, H, ptr(gt_c), ptr(d_c), ptr(mask_c), float(lo), float(hi), float(eps), ptr(used),
@@ -145,7 +150,7 @@ class _InverseDepthL1(torch.autograd.Function):
         H, W, lo, hi, eps, shape, dtype = ctx.cfg
         if v_out is None:
             return None, None, None, None, None, None
-        v = v_out.to(torch.float32).reshape(1).contiguous()
+        v = _cotangent(v_out)
         v_d = torch.empty_like(d_c)
         call("mtgs_inv_depth_l1_bwd", W, H, ptr(gt_c), ptr(d_c), ptr(mask_c), lo, hi, eps, ptr(v), ptr(out), ptr(v_d), stream_of(d_c))
         return None, v_d.reshape(shape).to(dtype), None, None, None, None
@@ -183,7 +188,7 @@ class _Combine(torch.autograd.Function):
     def backward(ctx, v_out):
         (kept,) = ctx.saved_tensors
         n, weights = ctx.cfg
-        v = v_out.to(torch.float32).reshape(1).contiguous()
+        v = _cotangent(v_out)
         v_terms = torch.empty(n, dtype=torch.float32, device=v.device)
         call("mtgs_loss_combine_bwd", n, ptr(v), ptr(kept), (C.c_float * n)(*weights), ptr(v_terms), stream_of(v))
         return v_terms, None, None, None
@@ -209,10 +214,10 @@ class _OutputHead(torch.autograd.Function):
         D = render.shape[-1]
         H, W = render.shape[-3], render.shape[-2]
         dev = render.device
-        r_c = render.detach().to(torch.float32).reshape(H, W, D).contiguous()
-        a_c = alpha.detach().to(torch.float32).reshape(H, W).contiguous()
-        bg_c = background.detach().to(torch.float32).reshape(3).contiguous()
-        e_c = None if exposure is None else exposure.detach().to(torch.float32).reshape(12).contiguous()
+        r_c = _as_f32(render, H, W, D)
+        a_c = _as_f32(alpha, H, W)
+        bg_c = _as_f32(background, 3)
+        e_c = None if exposure is None else _as_f32(exposure, 12)
         depth_ch = D - 1 if want_depth else -1
         dmax = r_c[..., depth_ch].max().reshape(1) if want_depth else None      # depth_im.detach().max() (:680)
         rgb = torch.empty((H, W, 3), dtype=torch.float32, device=dev)
@@ -239,9 +244,7 @@ class _OutputHead(torch.autograd.Function):
         need_bg, need_e = ctx.needs_input_grad[2], e_c is not None and ctx.needs_input_grad[3]
         v_bg = torch.empty(3, dtype=torch.float32, device=dev) if need_bg else None
         v_e = torch.empty(12, dtype=torch.float32, device=dev) if need_e else None
-        n = C.c_size_t(0)
-        call("mtgs_head_workspace_floats", W, H, C.byref(n))
-        partials = torch.empty(n.value, dtype=torch.float32, device=dev)
+        partials = workspace("mtgs_head_workspace_floats", W, H, device=dev, dtype=torch.float32)
         call("mtgs_head_bwd", W, H, D, depth_ch, normal_ch, ptr(r_c), ptr(a_c), ptr(bg_c), ptr(e_c), ptr(v_rgb), ptr(v_app),
              ptr(v_depth), ptr(v_normal), ptr(v_render), ptr(v_alpha), ptr(v_bg), ptr(v_e), ptr(partials), stream_of(r_c))
         return (v_render.reshape(r_shape), v_alpha.reshape(a_shape), None if v_bg is None else v_bg.reshape(bg_shape),
@@ -283,8 +286,8 @@ class _OobLoss(torch.autograd.Function):
         if load().mtgs_oob_desc_bytes() != _OOB_DESC.itemsize:
             raise RuntimeError("mtgs_oob_desc layout mismatch between libmtgs_rast.so and mtgs_amd.loss")
         n_nodes, dev = len(flat) // 2, radii.device
-        means = [m.detach().to(torch.float32).contiguous() for m in flat[0::2]]
-        opacs = [o.detach().to(torch.float32).reshape(-1).contiguous() for o in flat[1::2]]
+        means = [_as_f32(m) for m in flat[0::2]]
+        opacs = [_as_f32(o, -1) for o in flat[1::2]]
         n = np.asarray([m.shape[0] for m in means], dtype=np.int64)
         r = radii.reshape(-1)
         r = (r if r.dtype == torch.int32 else r.to(torch.int32)).contiguous()
@@ -319,7 +322,7 @@ class _OobLoss(torch.autograd.Function):
         tab = ctx.tab.copy()
         off = np.cumsum(ctx.tab["n"]) - ctx.tab["n"]
         tab["g_opacities"] = np.uint64(g_flat.data_ptr()) + np.uint64(4) * off.astype(np.uint64)
-        v = v_out.to(torch.float32).reshape(1).contiguous()
+        v = _cotangent(v_out)
         tab_dev = upload_table(tab, dev)
         call("mtgs_oob_bwd", n_nodes, ptr(tab_dev), ctx.blocks, ptr(flags), ptr(v), ptr(out), stream_of(out))
         grads = []
@@ -350,8 +353,8 @@ class _DepthNcc(torch.autograd.Function):
         require_gpu(pred, gt, mask)
         H, W = pred.shape[0], pred.shape[1]
         dev = pred.device
-        p_c = pred.detach().to(torch.float32).reshape(H, W).contiguous()
-        g_c = gt.detach().to(torch.float32).reshape(H, W).contiguous()
+        p_c = _as_f32(pred, H, W)
+        g_c = _as_f32(gt, H, W)
         m_c = _mask_u8(mask, H, W)
         n = C.c_int64(0)
         call("mtgs_ncc_patches", W, H, patch_size, stride, C.byref(n))
@@ -366,7 +369,7 @@ class _DepthNcc(torch.autograd.Function):
     def backward(ctx, v_out):
         p_c, g_c, stats, out = ctx.saved_tensors
         H, W, patch_size, stride, shape, dtype = ctx.cfg
-        v = v_out.to(torch.float32).reshape(1).contiguous()
+        v = _cotangent(v_out)
         v_pred = torch.empty_like(p_c)
         call("mtgs_ncc_bwd", W, H, patch_size, stride, ptr(p_c), ptr(g_c), ptr(stats), ptr(v), ptr(out), ptr(v_pred), stream_of(p_c))
         return v_pred.reshape(shape).to(dtype), None, None, None, None
@@ -392,10 +395,8 @@ class _TvLoss(torch.autograd.Function):
     def forward(ctx, image):
         require_gpu(image)
         H, W, Cc = image.shape[-3], image.shape[-2], image.shape[-1]
-        x = image.detach().to(torch.float32).reshape(H, W, Cc).contiguous()
-        n = C.c_size_t(0)
-        call("mtgs_tv_workspace_floats", W, H, Cc, C.byref(n))
-        partials = torch.empty(n.value, dtype=torch.float32, device=x.device)
+        x = _as_f32(image, H, W, Cc)
+        partials = workspace("mtgs_tv_workspace_floats", W, H, Cc, device=x.device, dtype=torch.float32)
         out = torch.empty(1, dtype=torch.float32, device=x.device)
         call("mtgs_tv_fwd", W, H, Cc, ptr(x), ptr(partials), ptr(out), stream_of(x))
         ctx.save_for_backward(x)
@@ -406,7 +407,7 @@ class _TvLoss(torch.autograd.Function):
     def backward(ctx, v_out):
         (x,) = ctx.saved_tensors
         H, W, Cc, shape, dtype = ctx.cfg
-        v = v_out.to(torch.float32).reshape(1).contiguous()
+        v = _cotangent(v_out)
         v_x = torch.empty_like(x)
         call("mtgs_tv_bwd", W, H, Cc, ptr(x), ptr(v), ptr(v_x), stream_of(x))
         return v_x.reshape(shape).to(dtype)
@@ -424,12 +425,12 @@ def _intrinsics(K: Tensor) -> Tensor:
     """K [3,3] (or [1,3,3]) as the fp32 row-major device array the kernels read fx, fy, cx, cy from (no host read: a
     float32 contiguous K is passed as it is, so a captured graph sees later writes into it)."""
     assert K.numel() == 9, K.shape
-    return K.detach().to(torch.float32).reshape(3, 3).contiguous()
+    return _as_f32(K, 3, 3)
 
 
 def _depth_image(depth: Tensor) -> Tensor:
     assert depth.dim() in (2, 3) and depth.numel() == depth.shape[0] * depth.shape[1], depth.shape
-    return depth.detach().to(torch.float32).reshape(depth.shape[0], depth.shape[1]).contiguous()
+    return _as_f32(depth, depth.shape[0], depth.shape[1])
 
 
 def normals_from_depth(depth: Tensor, K: Tensor) -> Tensor:
@@ -453,13 +454,11 @@ class _DepthNormalLoss(torch.autograd.Function):
     def forward(ctx, pred, gt_depth, K, mask, lo, hi, tv):
         require_gpu(pred, gt_depth, K, mask)
         H, W = pred.shape[0], pred.shape[1]
-        p_c = pred.detach().to(torch.float32).contiguous()
+        p_c = _as_f32(pred)
         d_c = _depth_image(gt_depth)
         k_c = _intrinsics(K)
         m_c = _mask_u8(mask, H, W)
-        n = C.c_size_t(0)
-        call("mtgs_depth_normal_loss_workspace_floats", W, H, C.byref(n))
-        partials = torch.empty(n.value, dtype=torch.float32, device=pred.device)
+        partials = workspace("mtgs_depth_normal_loss_workspace_floats", W, H, device=pred.device, dtype=torch.float32)
         out = torch.empty(4, dtype=torch.float32, device=pred.device)
         call("mtgs_depth_normal_loss_fwd", W, H, ptr(p_c), ptr(d_c), ptr(k_c), ptr(m_c), float(lo), float(hi), int(tv),
              ptr(partials), ptr(out), stream_of(pred))
@@ -471,7 +470,7 @@ class _DepthNormalLoss(torch.autograd.Function):
     def backward(ctx, v_out):
         p_c, d_c, k_c, m_c, out = ctx.saved_tensors
         H, W, lo, hi, tv, dtype = ctx.cfg
-        v = v_out.to(torch.float32).reshape(1).contiguous()
+        v = _cotangent(v_out)
         v_pred = torch.empty_like(p_c)
         call("mtgs_depth_normal_loss_bwd", W, H, ptr(p_c), ptr(d_c), ptr(k_c), ptr(m_c), lo, hi, tv, ptr(v), ptr(out),
              ptr(v_pred), stream_of(p_c))
@@ -504,11 +503,9 @@ class _ScaleRegularizers(torch.autograd.Function):
     @staticmethod
     def forward(ctx, scales, two_d, max_ratio):
         require_gpu(scales)
-        s = scales.detach().to(torch.float32).contiguous()
+        s = _as_f32(scales)
         N = s.shape[0]
-        n = C.c_size_t(0)
-        call("mtgs_scale_reg_workspace_floats", N, C.byref(n))
-        partials = torch.empty(n.value, dtype=torch.float32, device=s.device)
+        partials = workspace("mtgs_scale_reg_workspace_floats", N, device=s.device, dtype=torch.float32)
         out = torch.empty(2, dtype=torch.float32, device=s.device)
         call("mtgs_scale_reg_fwd", N, ptr(s), int(two_d), float(max_ratio), ptr(partials), ptr(out), stream_of(s))
         ctx.save_for_backward(s)

@@ -10,14 +10,13 @@ Forward only, no host reads (graph-capturable), bitwise reproducible.  The SSIM 
 """
 from __future__ import annotations
 
-import ctypes as C
 from typing import Dict, Optional
 
 import torch
 from torch import Tensor
 
-from ._lib import call, ptr, require_gpu, stream_of
-from .loss import _mask_u8
+from ._lib import call, ptr, require_gpu, stream_of, workspace
+from .loss import _as_f32, _mask_u8
 
 _EPS = 0.5 / 255
 
@@ -31,14 +30,8 @@ def _check_images(a: Tensor, b: Tensor, names) -> None:
         raise ValueError(f"{names[0]} {tuple(a.shape)} and {names[1]} {tuple(b.shape)} must have the same shape")
 
 
-def _image(t: Tensor) -> Tensor:
-    return t.detach().to(torch.float32).contiguous()
-
-
 def _workspace(P: int, num_iters: int, dev) -> Tensor:
-    n = C.c_size_t(0)
-    call("mtgs_metrics_workspace_bytes", P, num_iters, C.byref(n))
-    return torch.empty(n.value, dtype=torch.uint8, device=dev)
+    return workspace("mtgs_metrics_workspace_bytes", P, num_iters, device=dev, dtype=torch.uint8)
 
 
 def color_correct(img: Tensor, ref: Tensor, mask: Optional[Tensor] = None, num_iters: int = 5, eps: float = _EPS) -> Tensor:
@@ -48,7 +41,7 @@ def color_correct(img: Tensor, ref: Tensor, mask: Optional[Tensor] = None, num_i
     if num_iters < 0:
         raise ValueError(f"num_iters must be >= 0, got {num_iters}")
     require_gpu(img, ref, mask)
-    img_c, ref_c = _image(img), _image(ref)
+    img_c, ref_c = _as_f32(img), _as_f32(ref)
     H, W = img_c.shape[:2]
     out = torch.empty_like(img_c)
     if H * W == 0:
@@ -69,15 +62,14 @@ def image_metrics(pred: Tensor, gt: Tensor, mask: Optional[Tensor] = None, *, co
     if (pred_depth is None) != (lidar_depth is None):
         raise ValueError("pred_depth and lidar_depth must be given together")
     require_gpu(pred, gt, mask, pred_depth, lidar_depth)
-    pred_c, gt_c = _image(pred), _image(gt)
+    pred_c, gt_c = _as_f32(pred), _as_f32(gt)
     H, W = pred_c.shape[:2]
     P = H * W
     depths = None
     if pred_depth is not None:
         if pred_depth.numel() != P or lidar_depth.numel() != P:
             raise ValueError(f"depths must have H * W = {P} elements, got {pred_depth.numel()} and {lidar_depth.numel()}")
-        depths = (pred_depth.detach().to(torch.float32).reshape(H, W).contiguous(),
-                  lidar_depth.detach().to(torch.float32).reshape(H, W).contiguous())
+        depths = (_as_f32(pred_depth, H, W), _as_f32(lidar_depth, H, W))
     num_iters = 5 if color_corrected else 0
     if P == 0:
         out = torch.full((5,), float("nan"), dtype=torch.float32, device=pred_c.device)

@@ -318,3 +318,17 @@ def test_deferred_sh_dispatch_rules_on_cpu(monkeypatch):
     z = new()
     a, b = z + 0.5, z.sum()
     assert torch.equal(a * 1, ref + 0.5) and seen == [None]
+
+
+def test_reduction_helpers_are_defined_once():
+    """The fixed-order sums are a stated contract (bitwise reproducible results): each helper has ONE definition under csrc/."""
+    import re
+    from pathlib import Path
+    import mtgs_amd
+    csrc = Path(mtgs_amd.__file__).resolve().parent / "csrc"
+    text = "\n".join(p.read_text() for p in sorted(csrc.glob("*.h*")))
+    count = lambda name: len(re.findall(r"__device__ __forceinline__ \w+ %s\(" % name, text))
+    for name in ("block_sum4", "block_tree_sum_f64", "finish_sums", "row16_sum", "mul_rounded", "sgn0", "sgn_nan"):
+        assert count(name) == 1, name
+    for name in (r"block_sum(_256)?", "dpp_perm", "sgn"):
+        assert count(name) == 0, name

@@ -974,6 +974,30 @@ int mtgs_scale_reg_workspace_floats(int64_t n, size_t *nf);
 int mtgs_scale_reg_fwd(int64_t n, const float *scales, int two_d, float max_ratio, float *partials, float *out, void *stream);
 int mtgs_scale_reg_bwd(int64_t n, const float *scales, int two_d, float max_ratio, const float *v_out, float *v_scales, void *stream);
 
+/* ---- seeding a node from a point cloud (mtgs_amd/csrc/seed.hip): VanillaGaussianSplattingModel.populate_modules
+ * (vanilla_gaussian_splatting.py:114-196) without the host: sklearn's NearestNeighbors(n_neighbors = k + 1) with the first
+ * column dropped (k_nearest_sklearn, :372-390), then scales, rotations, colours and opacities of every point in one kernel.
+ * mtgs_knn: for every point the k smallest Euclidean distances to the OTHER points, ascending, dist [N, k]; idx [N, k]
+ *   (nullable) their indices, the smaller index first among equal distances.  Exact (an octree walk over a Morton-sorted
+ *   copy of the cloud), not approximate.  A distance is sqrt(((dx dx + dy dy) + dz dz)) with
+ *   dx = fl(a.x - b.x) ... in fp32 from the original coordinates: exact duplicates give exact zeros; the output is bitwise
+ *   reproducible and does not depend on the launch shape.  points: rows of three floats, row_stride floats apart (>= 3).
+ *   1 <= k <= 8, k < N < 2^31; N = 0 is a no-op.  status (DEVICE, [1]) = nonzero when a coordinate is not finite: then
+ *   nothing is searched, dist is NaN and idx -1.  ws: mtgs_knn_workspace_bytes(N, k) bytes, 16-byte aligned, no
+ *   initialisation.  No host reads, no allocation, no atomics.
+ * mtgs_seed_fwd: avg = mean(knn_dist[i, :k]);  scales[i, :scale_dim] = log(avg), and with normals and scale_dim = 3
+ *   scales[i, 2] = log(avg / 10) and quats[i] = matrix_to_quaternion(rotate_vector_to_vector((0, 0, 1), n / |n|))
+ *   (gaussian_model/utils.py:120-199, operation by operation in fp32: n = +z gives (1, 0, 0, 0), n = -z the reference's
+ *   non-unit (0, -0, -0, sqrt(2) / 2), a zero normal NaN);  without normals quats is not written (the caller draws random
+ *   rotations).  features_dc row 0 of point i (at features_dc + i * dc_row_stride) = (rgb / 255 - 0.5) / C0 for
+ *   sh_degree > 0, logit(rgb / 255, eps = 1e-10) for sh_degree = 0;  opacities[i] = logit(0.1).  rgb [N, 3] in 0..255,
+ *   normals [N, 3] nullable, scale_dim 1 or 3, quats nullable unless it is written. */
+int mtgs_knn_workspace_bytes(int64_t N, int k, size_t *bytes);
+int mtgs_knn(int64_t N, int k, const float *points, int64_t row_stride, float *dist, int32_t *idx, int32_t *status,
+             void *ws, size_t ws_bytes, void *stream);
+int mtgs_seed_fwd(int64_t N, int k, const float *knn_dist, const float *rgb, const float *normals, int sh_degree, int scale_dim,
+                  float *scales, float *quats, float *features_dc, int64_t dc_row_stride, float *opacities, void *stream);
+
 /* ---- SURVEY.md section 8f, rank 2 (second half): the optimizer step of every Gaussian parameter group in ONE launch ----
  * Reference: one torch.optim.Adam per parameter group with one tensor each (mtgs/scene_model/custom_trainer.py:115-136;
  * groups, learning rates and eps = 1e-15 in mtgs/config/MTGS.py:121-181); the densification moves the moments with their

@@ -9,15 +9,17 @@ does, and raises if libmtgs_rast.so has not been built (python -m mtgs_amd.build
 Beyond gsplat's surface: `mtgs_amd.graph_mode` / `mtgs_amd.graphs.GraphedIteration` (an iteration as one HIP graph launch),
 `mtgs_amd.tight_lists` (opt-in shorter tile lists), `mtgs_amd.dist` (view-parallel data parallelism), `mtgs_amd.nodes` / `.loss`
 / `.densify` / `.optim` (the fused neighbours of the path), `mtgs_amd.appearance` (WildGaussians.py's appearance colours: `wild_colors`,
-`wild_color_source`), `mtgs_amd.metrics` (get_metrics_dict's image metrics: `color_correct`, `image_metrics`).
+`wild_color_source`), `mtgs_amd.metrics` (get_metrics_dict's image metrics: `color_correct`, `image_metrics`), `mtgs_amd.seed`
+(populate_modules: a node from a point cloud -- `knn_distances`, `seed_gaussians`, `sky_points`).
 """
 from .appearance import wild_color_source, wild_colors
 from .metrics import color_correct, image_metrics
 from .rendering import rasterization
+from .seed import knn_distances, seed_gaussians, sky_points
 from .wrapper import (exact_lists, fully_fused_projection, graph_mode, isect_offset_encode, isect_tiles, lists_are_tight,
                       rasterize_to_pixels, sh_lazy, sh_prefill, spherical_harmonics, tight_lists)
 
 __version__ = "0.1.0"
 __all__ = ["rasterization", "spherical_harmonics", "fully_fused_projection", "isect_tiles",
            "isect_offset_encode", "rasterize_to_pixels", "graph_mode", "exact_lists", "tight_lists", "lists_are_tight", "sh_prefill", "sh_lazy",
-           "wild_colors", "wild_color_source", "color_correct", "image_metrics"]
+           "wild_colors", "wild_color_source", "color_correct", "image_metrics", "knn_distances", "seed_gaussians", "sky_points"]

@@ -26,9 +26,9 @@ COMMON_FLAGS = [
     "-Wall", "-Wno-unused-function", f"-I{PKG.parent / 'include'}",
 ]
 # The projection forward must round after every operation (bit-exact tile binning inputs); the metrics and the
-# geometric losses round as the reference's per-operation PyTorch kernels do.
+# geometric losses round as the reference's per-operation PyTorch kernels do, and so do the neighbour distances and the seeding.
 PER_FILE_FLAGS = {"project.hip": ["-ffp-contract=off"], "front.hip": ["-ffp-contract=off"], "metrics.hip": ["-ffp-contract=off"],
-                  "geomloss.hip": ["-ffp-contract=off"]}
+                  "geomloss.hip": ["-ffp-contract=off"], "seed.hip": ["-ffp-contract=off"]}
 
 
 class HipccNotFound(RuntimeError):

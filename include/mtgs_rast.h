@@ -998,6 +998,37 @@ int mtgs_knn(int64_t N, int k, const float *points, int64_t row_stride, float *d
 int mtgs_seed_fwd(int64_t N, int k, const float *knn_dist, const float *rgb, const float *normals, int sh_degree, int scale_dim,
                   float *scales, float *quats, float *features_dc, int64_t dc_row_stride, float *opacities, void *stream);
 
+/* ---- preparing the seeding point cloud (mtgs_amd/csrc/cloud.hip): NuPlanDataparser._load_3D_points
+ * (mtgs/dataset/nuplan_dataparser.py:460-500) without open3d: remove_statistical_outlier and voxel_down_sample on the device.
+ * Additive block: MTGS_RAST_ABI_VERSION stays 28 and MTGS_RAST_HOT_ABI_VERSION 7 (no existing kernel or signature changes).
+ * points: rows of three floats, row_stride floats apart (>= 3), so a [N, 4][:, :3] view is read in place.  0 <= N < 2^31;
+ * N = 0 is a no-op.  ws: *_workspace_bytes(...) bytes, 16-byte aligned, no initialisation.  No host reads, no allocation, no
+ * float atomics; the host checks name the bad argument (mtgs_rast_last_error).
+ * mtgs_cloud_outlier: open3d's statistics.  k = min(nb_neighbors, N), 2 <= nb_neighbors <= 32.  avg[i] (f64 [N]) = (sum of the
+ *   distances from point i to its k - 1 nearest OTHER points) / k: the mean over a k-neighbour query that returns the point
+ *   itself at distance 0.  The search is mtgs_knn's exact octree walk (fp32 d2 = ((dx dx + dy dy) + dz dz), ties by the
+ *   smaller index); the sum is sqrt((double)d2) added in fp64 in ascending (d2, index) order, so avg is bitwise independent of
+ *   the launch shape, the run and the order of the rows.  stats (f64 [4]) = {cloud_mean, std, threshold, valid}: valid = N,
+ *   cloud_mean = (sum of avg over avg > 0) / valid, std = sqrt((sum of (avg - cloud_mean)^2 over avg > 0) / (valid - 1)),
+ *   threshold = cloud_mean + std_ratio * std, in fixed-order fp64 trees.  keep[i] (u8 [N]) = avg[i] > 0 && avg[i] < threshold:
+ *   a point with k - 1 exact duplicates has avg = 0 and is dropped, N = 1 gives a NaN threshold and keeps nothing, as in
+ *   open3d.  status (DEVICE, [1]) = nonzero when a coordinate is not finite: then nothing is searched and avg is NaN.
+ * mtgs_cloud_voxel: voxel_min_bound = min_bound - voxel_size * 0.5 and index = floor(((double)p - voxel_min_bound) /
+ *   voxel_size) per axis in fp64 (one subtraction, one division); key = ix << 42 | iy << 21 | iz.  Voxel v of the M occupied
+ *   ones, in ascending key order (open3d's order is that of a hash map; nothing downstream depends on it), gets out_xyz[v]
+ *   and out_rgb[v] (f64 [N, 3] capacity, M rows written) = the sums of its points' coordinates and colours, added in fp64 in
+ *   ascending original index from 0, divided once by the count; counts[v] (i32 [N] capacity); out_keys[v] (i64, nullable).
+ *   colors [N, 3] contiguous: uint8 (colors_u8 != 0; a channel is (double)c / 255.0) or float32 in [0, 1].  n_voxels (DEVICE,
+ *   [1]) = M.  status (DEVICE, [1]): bit 0 = a coordinate is not finite, bit 1 / 2 / 3 = the x / y / z index needs more than
+ *   21 bits; with a nonzero status the outputs are meaningless.  voxel_size > 0 and finite. */
+int mtgs_cloud_outlier_workspace_bytes(int64_t N, int nb_neighbors, size_t *bytes);
+int mtgs_cloud_outlier(int64_t N, int nb_neighbors, double std_ratio, const float *points, int64_t row_stride, double *avg,
+                       double *stats, uint8_t *keep, int32_t *status, void *ws, size_t ws_bytes, void *stream);
+int mtgs_cloud_voxel_workspace_bytes(int64_t N, size_t *bytes);
+int mtgs_cloud_voxel(int64_t N, double voxel_size, const float *points, int64_t row_stride, const void *colors, int colors_u8,
+                     double *out_xyz, double *out_rgb, int32_t *counts, int64_t *out_keys, int32_t *n_voxels, int32_t *status,
+                     void *ws, size_t ws_bytes, void *stream);
+
 /* ---- SURVEY.md section 8f, rank 2 (second half): the optimizer step of every Gaussian parameter group in ONE launch ----
  * Reference: one torch.optim.Adam per parameter group with one tensor each (mtgs/scene_model/custom_trainer.py:115-136;
  * groups, learning rates and eps = 1e-15 in mtgs/config/MTGS.py:121-181); the densification moves the moments with their

@@ -10,10 +10,12 @@ Beyond gsplat's surface: `mtgs_amd.graph_mode` / `mtgs_amd.graphs.GraphedIterati
 `mtgs_amd.tight_lists` (opt-in shorter tile lists), `mtgs_amd.dist` (view-parallel data parallelism), `mtgs_amd.nodes` / `.loss`
 / `.densify` / `.optim` (the fused neighbours of the path), `mtgs_amd.appearance` (WildGaussians.py's appearance colours: `wild_colors`,
 `wild_color_source`), `mtgs_amd.metrics` (get_metrics_dict's image metrics: `color_correct`, `image_metrics`), `mtgs_amd.seed`
-(populate_modules: a node from a point cloud -- `knn_distances`, `seed_gaussians`, `sky_points`).
+(populate_modules: a node from a point cloud -- `knn_distances`, `seed_gaussians`, `sky_points`), `mtgs_amd.pointcloud`
+(_load_3D_points: the cloud that node is seeded from -- `statistical_outlier_removal`, `voxel_down_sample`, `prepare_seed_cloud`).
 """
 from .appearance import wild_color_source, wild_colors
 from .metrics import color_correct, image_metrics
+from .pointcloud import prepare_seed_cloud, statistical_outlier_removal, voxel_down_sample
 from .rendering import rasterization
 from .seed import knn_distances, seed_gaussians, sky_points
 from .wrapper import (exact_lists, fully_fused_projection, graph_mode, isect_offset_encode, isect_tiles, lists_are_tight,
@@ -22,4 +24,5 @@ from .wrapper import (exact_lists, fully_fused_projection, graph_mode, isect_off
 __version__ = "0.1.0"
 __all__ = ["rasterization", "spherical_harmonics", "fully_fused_projection", "isect_tiles",
            "isect_offset_encode", "rasterize_to_pixels", "graph_mode", "exact_lists", "tight_lists", "lists_are_tight", "sh_prefill", "sh_lazy",
-           "wild_colors", "wild_color_source", "color_correct", "image_metrics", "knn_distances", "seed_gaussians", "sky_points"]
+           "wild_colors", "wild_color_source", "color_correct", "image_metrics", "knn_distances", "seed_gaussians", "sky_points",
+           "statistical_outlier_removal", "voxel_down_sample", "prepare_seed_cloud"]

@@ -164,6 +164,10 @@ _SIGNATURES = {
     "mtgs_knn_workspace_bytes": [_i64, _i32, C.POINTER(_sz)],
     "mtgs_knn": [_i64, _i32, _vp, _i64, _vp, _vp, _vp, _vp, _sz, _vp],
     "mtgs_seed_fwd": [_i64, _i32, _vp, _vp, _vp, _i32, _i32, _vp, _vp, _vp, _i64, _vp, _vp],
+    "mtgs_cloud_outlier_workspace_bytes": [_i64, _i32, C.POINTER(_sz)],
+    "mtgs_cloud_outlier": [_i64, _i32, C.c_double, _vp, _i64, _vp, _vp, _vp, _vp, _vp, _sz, _vp],
+    "mtgs_cloud_voxel_workspace_bytes": [_i64, C.POINTER(_sz)],
+    "mtgs_cloud_voxel": [_i64, C.c_double, _vp, _i64, _vp, _i32, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _sz, _vp],
     "mtgs_adam_group_bytes": [],
     "mtgs_adam_block_elems": [],
     "mtgs_adam_block_rows": [],

@@ -132,7 +132,7 @@ __global__ __launch_bounds__(256) void mean_or_zero_finish_kernel(int64_t nblock
     if (threadIdx.x == 0) { out[0] = tc > 0.f ? ts / tc : 0.f; out[1] = tc; }
 }
 
-// v_Y[q] = (v_out / count) * sum_p w2d(q - p) * (g_mu[p] + 2 Y[q] g_e22[p] + X[q] g_e12[p])
+// v_Y[q] = (v_out / count, 0 when count = 0) * sum_p w2d(q - p) * (g_mu[p] + 2 Y[q] g_e22[p] + X[q] g_e12[p])
 __global__ __launch_bounds__(256) void ssim_bwd_kernel(int H, int W, const float *__restrict__ X, const float *__restrict__ Y,
                                                        const float *__restrict__ gmaps, const Window win,
                                                        const float *__restrict__ v_out, const float *__restrict__ fwd_out,
@@ -143,7 +143,8 @@ __global__ __launch_bounds__(256) void ssim_bwd_kernel(int H, int W, const float
     const int tid = threadIdx.x, tx = tid & 15, ty = tid >> 4;
     const int x0 = blockIdx.x * TILE, y0 = blockIdx.y * TILE;
     const int px = x0 + tx, py = y0 + ty;
-    const float scale = v_out[0] / fwd_out[1];
+    // an empty selection: the reference's mean is NaN but scatters nothing back, the gradient is zero (not 0 * v / 0 = NaN)
+    const float scale = fwd_out[1] > 0.f ? v_out[0] / fwd_out[1] : 0.f;
     // (the next channel's maps and pixels are fetched while the current channel is filtered, as in the forward)
     constexpr int PER = (IN_TILE * IN_TILE + 255) / 256;
     float rg[PER][3], xn = 0.f, yn = 0.f;

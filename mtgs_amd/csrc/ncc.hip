@@ -72,7 +72,8 @@ __global__ __launch_bounds__(NCC_BLOCK) void ncc_bwd_kernel(NccGrid G, const flo
     const int64_t q = (int64_t)blockIdx.x * NCC_BLOCK + threadIdx.x;
     if (q >= (int64_t)G.H * G.W) return;
     const int y = (int)(q / G.W), x = (int)(q - (int64_t)y * G.W);
-    const float scale = -v_out[0] / (fwd_out[1] * (float)(G.k * G.k));
+    // no valid patch: the reference's mean of an empty tensor is NaN and sends no gradient (zero, not 0 * v / 0 = NaN)
+    const float scale = fwd_out[1] > 0.f ? -v_out[0] / (fwd_out[1] * (float)(G.k * G.k)) : 0.f;
     const float p = pred[q], g = gt[q];
     // patches (i, j) with i*s - pad <= y < i*s - pad + k
     const int i_hi = min((y + G.pad) / G.s, G.Lh - 1), i_lo = max((y + G.pad - G.k + G.s) / G.s, 0);   // ceil((y+pad-k+1)/s)

@@ -5,7 +5,7 @@
 //     loss   = mean(|h_diff|) + mean(|w_diff|)
 // (PyTorch: two slice pairs, abs, two means forward; four zero-filled full-size gradients and their adds backward.)
 // Forward: per-block partial sums of both terms in a fixed order; backward: thread per element gathering the signs of
-// its (up to) four differences.  NaN inputs propagate as in the reference (MTGS drops the term when it is not finite).
+// its (up to) four differences.  NaN inputs propagate to the value as in the reference (MTGS drops the term when it is not finite).
 #include "common.hpp"
 #include "block_reduce.hpp"
 
@@ -36,7 +36,8 @@ __global__ __launch_bounds__(TV_BLOCK) void tv_finish_kernel(int64_t nblocks, fl
     if (threadIdx.x == 0) out[0] = ta * inv_a + tb * inv_b;
 }
 
-__device__ __forceinline__ float sgn_nan(float d) { return d > 0.f ? 1.f : (d < 0.f ? -1.f : (d == 0.f ? 0.f : d)); }   // NaN stays NaN (geomloss.hip's sgn0 drops it)
+// torch.abs's backward is grad * sign(x), and torch.sign(NaN) = 0: a NaN pixel makes the VALUE NaN, the gradient stays finite
+__device__ __forceinline__ float sgn_nan(float d) { return d > 0.f ? 1.f : (d < 0.f ? -1.f : 0.f); }
 
 __global__ __launch_bounds__(TV_BLOCK) void tv_bwd_kernel(int H, int W, int C, const float *__restrict__ x, const float *__restrict__ v_out,
                                                           float inv_a, float inv_b, float *__restrict__ v_x) {
@@ -84,6 +85,8 @@ extern "C" int mtgs_tv_bwd(int width, int height, int channels, const float *ima
     MTGS_REQUIRE(image && v_out && v_image, MTGS_EINVAL, "mtgs_tv_bwd: null pointer");
     float ia, ib;
     scales_of(height, width, channels, ia, ib);
+    if (width == 1) ia = 0.f;      // an empty difference tensor: its NaN mean sends no gradient (autograd scatters nothing back)
+    if (height == 1) ib = 0.f;
     tv_bwd_kernel<<<(unsigned)ceil_div64((int64_t)width * height * channels, TV_BLOCK), TV_BLOCK, 0, (hipStream_t)stream>>>(
         height, width, channels, image, v_out, ia, ib, v_image);
     MTGS_CHECK_LAUNCH("mtgs_tv_bwd");

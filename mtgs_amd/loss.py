@@ -72,7 +72,9 @@ def masked_ssim(gt: Tensor, pred: Tensor, mask: Optional[Tensor] = None, win_sig
                 data_range: float = 1.0, K: Tuple[float, float] = (0.01, 0.03)) -> Tensor:
     """gt, pred: [H, W, 3]; mask: [H, W, 1] / [H, W] bool or None.  Returns the scalar the reference's MaskedSSIM
     returns (mean of the SSIM map over the masked elements; the mask is cropped by the 5-pixel window margin).
-    Differentiable with respect to `pred` (the reference's second argument); `gt` gets no gradient."""
+    Differentiable with respect to `pred` (the reference's second argument); `gt` gets no gradient.  A mask that selects
+    nothing (all false, or true only inside the cropped margin) gives NaN with a ZERO gradient, as autograd through the
+    reference's ssim_map[mask].mean() does."""
     assert pred.dim() == 3 and pred.shape[2] == 3 and gt.shape == pred.shape, (gt.shape, pred.shape)
     H, W = pred.shape[:2]
     if H <= 10 or W <= 10:
@@ -381,7 +383,8 @@ def depth_ncc_loss(pred_depth: Tensor, gt_depth: Tensor, patch_size: int = 32, s
     (/root/reference/mtgs/utils/geometric_loss.py:322-348; called at mtgs_scene_graph.py:886-894 with the config's
     ncc_patch_size = 32, ncc_stride = 16): one minus the mean, over the patches whose mask is entirely set, of the normalised
     cross-correlation between the two depth images.  pred_depth, gt_depth [H,W,1] (or [H,W]), mask [H,W,1] bool.  Two
-    launches forward, one backward, no host synchronisation; differentiable with respect to pred_depth."""
+    launches forward, one backward, no host synchronisation; differentiable with respect to pred_depth.  Without a valid
+    patch the value is NaN (the reference's mean of an empty tensor) and the gradient zero."""
     assert pred_depth.dim() in (2, 3) and pred_depth.numel() == pred_depth.shape[0] * pred_depth.shape[1], pred_depth.shape
     assert gt_depth.numel() == pred_depth.numel() and (mask is None or mask.numel() == pred_depth.numel()), (gt_depth.shape,)
     assert patch_size > 0 and stride > 0
@@ -416,7 +419,9 @@ class _TvLoss(torch.autograd.Function):
 def tv_loss(image: Tensor) -> Tensor:
     """TVLoss()(image) of MTGS's normal term (/root/reference/mtgs/utils/geometric_loss.py:293-303, used at
     mtgs_scene_graph.py:931-932): mean |image[:, :-1] - image[:, 1:]| + mean |image[:-1] - image[1:]| for one image
-    [H,W,C] (or [1,H,W,C]).  Two launches forward, one backward."""
+    [H,W,C] (or [1,H,W,C]).  Two launches forward, one backward.  A one-pixel-wide (or -high) image has an empty difference
+    tensor: the value is NaN, that half sends no gradient.  A NaN pixel makes the value NaN; the gradient follows
+    torch.sign(NaN) = 0 and stays finite."""
     assert image.dim() in (3, 4) and (image.dim() == 3 or image.shape[0] == 1), image.shape
     return _TvLoss.apply(image)
 

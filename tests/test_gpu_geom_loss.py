@@ -14,6 +14,9 @@ import numpy as np
 import pytest
 import torch
 
+from tests.image_refs import normals_from_depth_ref as _normals_f64, scale_reg_rule_grad as _rule_grad, \
+    scale_reg_values as _scale_reg_f64, scene_depth as _scene_depth
+
 pytestmark = pytest.mark.gpu
 
 GOLDEN = Path(__file__).resolve().parent / "golden" / "depth_normals_ref.npz"
@@ -66,35 +69,6 @@ def test_depth_normal_loss_and_gradient_match_the_reference():
         torch.testing.assert_close(got[~near], g_ref[~near], rtol=1e-5, atol=1e-10, msg=lambda m: f"{c}: {m}")
 
 
-def _scene_depth(H, W, seed):
-    """a street-like depth image: a ground plane below the horizon, smooth facades above it, a few step edges"""
-    g = torch.Generator().manual_seed(seed)
-    v = torch.arange(H, dtype=torch.float64)[:, None] + 0.5
-    u = torch.arange(W, dtype=torch.float64)[None, :] + 0.5
-    ground = 1.6 * 0.8 * W / torch.clamp(v - H / 2, min=1e-3)
-    facade = 12.0 + 4.0 * torch.sin(u / W * 9.0) + 2.0 * ((u / W * 7).floor() % 2)
-    d = torch.where(v > H / 2 + 2, torch.minimum(ground, facade + 30), facade)
-    d = d + 0.002 * torch.rand(H, W, generator=g, dtype=torch.float64)
-    return d.float()[..., None]
-
-
-def _normals_f64(depth, K):
-    """normal_from_depth_image -> flip -> (1 + n) / 2 in float64, restated from its description"""
-    d = depth.double()[..., 0]
-    H, W = d.shape
-    K = K.double()
-    u = torch.arange(W, dtype=torch.float64, device=d.device)[None, :] + 0.5
-    v = torch.arange(H, dtype=torch.float64, device=d.device)[:, None] + 0.5
-    P = torch.stack([(u - K[0, 2]) * d / K[0, 0], (v - K[1, 2]) * d / K[1, 1], d], dim=-1)
-    a = P[1:-1, 2:] - P[1:-1, :-2]
-    b = P[:-2, 1:-1] - P[2:, 1:-1]
-    n = torch.nn.functional.normalize(torch.cross(a, b, dim=-1), dim=-1)
-    out = torch.zeros(H, W, 3, dtype=torch.float64, device=d.device)
-    out[1:-1, 1:-1] = n
-    out[..., 1:] *= -1
-    return (1 + out) / 2
-
-
 @pytest.mark.parametrize("W,H", [(960, 540), (1920, 1080)])
 def test_depth_normal_loss_full_size_against_float64(W, H):
     from mtgs_amd.loss import depth_normal_loss, normals_from_depth
@@ -106,7 +80,7 @@ def test_depth_normal_loss_full_size_against_float64(W, H):
     pred = torch.rand(H, W, 3, generator=g).cuda().requires_grad_(True)
     mask = torch.ones(H, W, 1, dtype=torch.bool, device="cuda")
     mask[: H // 8] = False
-    n64 = _normals_f64(depth, K)
+    n64 = _normals_f64(depth.cpu(), K.cpu()).cuda()
     got = normals_from_depth(depth, K)
     err = (got.double() - n64).abs().max().item()
     assert err < 2e-4, err
@@ -168,17 +142,6 @@ def test_empty_selection_gives_nan():
     assert abs(float(depth_normal_loss(pred, depth, K)) - float(l1 + tv)) <= 1e-6
 
 
-def _scale_reg_f64(s, two_d, r):
-    two = torch.min(s, dim=1, keepdim=True)[0].mean()
-    if two_d:
-        srt, _ = torch.sort(s, dim=-1, descending=True)
-        ratio = srt[..., 0] / srt[..., 1]
-    else:
-        ratio = s.amax(dim=-1) / s.amin(dim=-1)
-    sharp = (torch.maximum(ratio, torch.tensor(r, dtype=s.dtype)) - r).mean()
-    return two, sharp
-
-
 @pytest.mark.parametrize("two_d", [True, False])
 def test_scale_regularizers_against_float64_autograd(two_d):
     from mtgs_amd.loss import scale_regularizers
@@ -200,32 +163,6 @@ def test_scale_regularizers_against_float64_autograd(two_d):
     clear = (ratio - 10.0).abs() > 1e-4
     assert clear.float().mean() > 0.999
     torch.testing.assert_close(grad.cpu().double()[clear], g64[clear], rtol=2e-5, atol=1e-13)
-
-
-def _rule_grad(row, two_d, r, N, v0, v1):
-    """the documented rules of include/mtgs_rast.h, for one row, in float64"""
-    s = [float(x) for x in row]
-    g = [0.0, 0.0, 0.0]
-    g[min(range(3), key=lambda i: (s[i], i))] += v0 / N
-    hi = max(range(3), key=lambda i: (s[i], -i))
-    if two_d:
-        lo = max((i for i in range(3) if i != hi), key=lambda i: (s[i], -i))
-    else:
-        lo = min(range(3), key=lambda i: (s[i], i))
-    sa, sb = s[hi], s[lo]
-    ratio = sa / sb
-    f = 0.0 if ratio < r else (0.5 if ratio == r else 1.0)
-    da, db = v1 / N * f / sb, -(v1 / N * f) * sa / (sb * sb)
-    if two_d:
-        g[hi] += da
-        g[lo] += db
-    else:
-        for j in range(3):
-            if s[j] == sa:
-                g[j] += da / sum(x == sa for x in s)
-            if s[j] == sb:
-                g[j] += db / sum(x == sb for x in s)
-    return g
 
 
 def test_scale_regularizers_tie_rules():

@@ -55,6 +55,7 @@ def test_masked_l1_matches_torch_formulation(hip_lib, use_mask, ch):
     """mtgs_scene_graph.py:823: torch.abs(gt_img - pred)[combined_mask.squeeze(-1)].mean(); one channel: the depth terms
     (:881-883, mask [H,W,1] indexing [H,W,1] images), three: the normal term (:934)."""
     from mtgs_amd.loss import masked_l1
+    from tests.image_refs import masked_l1_ref
     dev = torch.device("cuda")
     g = torch.Generator().manual_seed(3)
     H, W = 211, 333
@@ -62,15 +63,12 @@ def test_masked_l1_matches_torch_formulation(hip_lib, use_mask, ch):
     pred0 = torch.rand(H, W, ch, generator=g)
     pred0[5, 7] = gt[5, 7].cpu()                                    # exact ties: sign(0) = 0
     mask = (torch.rand(H, W, 1, generator=g) > 0.4).to(dev) if use_mask else None
-    p_ref = pred0.to(dev).double().requires_grad_(True)
-    d = torch.abs(gt.double() - p_ref)
-    ref = d[mask.squeeze(-1)].mean() if use_mask else d.mean()
-    (0.8 * ref).backward()
+    ref, g_ref = masked_l1_ref(gt.cpu(), pred0, None if mask is None else mask.cpu())
     p = pred0.to(dev).requires_grad_(True)
     val = masked_l1(gt, p, mask)
     (0.8 * val).backward()
-    assert abs(float(val.detach()) - float(ref.detach())) <= 2e-6
-    assert torch.allclose(p.grad.double(), p_ref.grad, rtol=1e-5, atol=1e-12)
+    assert abs(float(val.detach()) - float(ref)) <= 2e-6
+    assert torch.allclose(p.grad.cpu().double(), 0.8 * g_ref, rtol=1e-5, atol=1e-12)
 
 
 def test_combine_losses_matches_the_written_out_sum(hip_lib):
@@ -100,6 +98,7 @@ def test_inverse_depth_l1_matches_the_reference_formulation(hip_lib, use_mask, e
     combined with the image mask, |1 / (gt + 1e-5) - 1 / (pred + 1e-5)| over it, 0 for an empty mask; value, gradient with
     respect to the predicted depth, and the mask by-product (the NCC term's mask, :891)."""
     from mtgs_amd.loss import inverse_depth_l1
+    from tests.image_refs import inverse_depth_l1_ref
     dev = torch.device("cuda")
     g = torch.Generator().manual_seed(4)
     H, W = 135, 241
@@ -111,22 +110,13 @@ def test_inverse_depth_l1_matches_the_reference_formulation(hip_lib, use_mask, e
     pred0[3, 4] = gt[3, 4]                                        # an exact tie inside the range: sign(0) = 0
     gt = gt.to(dev)
     mask = (torch.rand(H, W, 1, generator=g) > 0.3).to(dev) if use_mask else None
-    m_ref = (gt > 0.1) & (gt < 80)
-    if use_mask:
-        m_ref = m_ref & mask
-    p_ref = pred0.to(dev).double().requires_grad_(True)
-    if int(m_ref.sum()) == 0:
-        ref = torch.zeros((), dtype=torch.float64, device=dev)
-    else:
-        ref = torch.abs(1 / (gt.double() + 1e-5) - 1 / (p_ref + 1e-5))[m_ref].mean()
-        (0.5 * ref).backward()
+    ref, g_ref, m_ref = inverse_depth_l1_ref(pred0, gt.cpu(), None if mask is None else mask.cpu())
     p = pred0.to(dev).requires_grad_(True)
     val, m = inverse_depth_l1(p, gt, mask)
     (0.5 * val).backward()
-    assert m.dtype == torch.bool and m.shape == (H, W, 1) and torch.equal(m, m_ref)
+    assert m.dtype == torch.bool and m.shape == (H, W, 1) and torch.equal(m.cpu(), m_ref)
     assert abs(float(val) - float(ref)) <= 2e-6 * max(1.0, abs(float(ref)))
-    want = p_ref.grad if p_ref.grad is not None else torch.zeros_like(p_ref)
-    assert torch.allclose(p.grad.double(), want, rtol=2e-5, atol=1e-12)
+    assert torch.allclose(p.grad.cpu().double(), 0.5 * g_ref, rtol=2e-5, atol=1e-12)
 
 
 @pytest.mark.parametrize("D,with_exposure,with_depth,normal_ch", [(8, True, True, 3), (4, True, True, -1), (3, False, False, -1),
@@ -137,6 +127,7 @@ def test_output_head_matches_the_reference_formulation(hip_lib, D, with_exposure
     exposure) to 2e-5 relative.  Values are kept away from the clamp edges by construction of the cotangent test only where
     the reference itself is continuous; exact edge hits are covered by the inclusive-mask rule (0 and 1 pass)."""
     from mtgs_amd.loss import output_head
+    from tests.image_refs import output_head_ref
     dev = torch.device("cuda")
     g = torch.Generator().manual_seed(D * 7 + normal_ch)
     H, W = 97, 131
@@ -152,19 +143,6 @@ def test_output_head_matches_the_reference_formulation(hip_lib, D, with_exposure
     cots = [torch.randn(H, W, 3, generator=g), torch.randn(H, W, 3, generator=g), torch.randn(H, W, 1, generator=g),
             torch.randn(H, W, 3, generator=g)]
 
-    def reference(render, alpha, bg, E):
-        rgb = torch.clamp(render[..., :3] + (1 - alpha) * bg, 0.0, 1.0).squeeze(0)
-        app = torch.clamp(rgb.matmul(E[:3, :3]) + E[None, None, :3, 3], 0, 1) if E is not None else None
-        depth = None
-        if with_depth:
-            d = render[..., -1:]
-            depth = torch.where(alpha > 0, d, d.detach().max()).squeeze(0)
-        normal = None
-        if normal_ch >= 0:
-            n = render[..., normal_ch:normal_ch + 3].squeeze(0)
-            normal = (n / n.norm(dim=-1, keepdim=True) + 1) / 2
-        return rgb, app, depth, normal
-
     def run(fn, dtype, device):
         P = [t.to(device=device, dtype=dtype).requires_grad_(True) if t is not None else None for t in (render, alpha, bg, E)]
         outs = fn(*P)
@@ -172,7 +150,7 @@ def test_output_head_matches_the_reference_formulation(hip_lib, D, with_exposure
         loss.backward()
         return outs, [None if p is None else p.grad for p in P]
 
-    ref_out, ref_grad = run(reference, torch.float64, "cpu")
+    ref_out, ref_grad = output_head_ref(render, alpha, bg, E, cots, with_depth, normal_ch)
     out, grad = run(lambda r, a, b, e: output_head(r, a, b, e, depth=with_depth, normal_channel=normal_ch), torch.float32, dev)
     for o, r, name in zip(out, ref_out, ("rgb", "rgb_appearance", "depth", "normal")):
         assert (o is None) == (r is None), name
@@ -196,6 +174,7 @@ def test_oob_loss_matches_the_reference_loop(hip_lib, n_nodes):
     """mtgs_amd.loss.oob_loss against the per-node loop of mtgs_scene_graph.py:949-967 written out in torch float64
     (model_id comparison, visible-node test, |means| > size / 2 + tolerance, -log(1 - sigmoid + 1e-6), mean)."""
     from mtgs_amd.loss import oob_loss
+    from tests.image_refs import oob_ref
     dev = torch.device("cuda")
     g = torch.Generator().manual_seed(n_nodes + 11)
     sizes = [int(x) for x in torch.randint(1, 700, (n_nodes,), generator=g)]
@@ -214,31 +193,16 @@ def test_oob_loss_matches_the_reference_loop(hip_lib, n_nodes):
         means = torch.randn(k, 3, generator=g) * 2.0
         nodes.append((means, torch.randn(k, 1, generator=g) * 2, [2.0 + torch.rand(1, generator=g).item(), 1.5, 4.0]))
 
-    # reference loop, float64
-    ops = [o.double().requires_grad_(True) for _, o, _ in nodes]
-    visible = (radii > 0).flatten()
-    loss, count = 0.0, 0
-    for (means, _, size), o, st, k in zip(nodes, ops, starts, sizes):
-        if visible[st:st + k].sum() == 0:
-            continue
-        oob = (means.double().abs() > (torch.tensor(size, dtype=torch.float64) / 2 + 1.5)[None]).any(-1)
-        if oob.sum() != 0:
-            loss = loss + (-torch.log(1 - o[oob].sigmoid() + 1e-6)).sum()
-            count += int(oob.sum())
-    ref = loss / count if count else torch.zeros((), dtype=torch.float64)
-    if count:
-        (3.0 * ref).backward()
+    ref, g_ref = oob_ref(nodes, radii, starts, tolerance=1.5)
 
     P = [o.to(dev).requires_grad_(True) for _, o, _ in nodes]
     val = oob_loss([(m.to(dev), p, size) for (m, _, size), p in zip(nodes, P)], radii.to(dev), starts, tolerance=1.5)
-    ref = ref.detach() if torch.is_tensor(ref) else ref
     assert abs(float(val.detach()) - float(ref)) <= 2e-5 * max(1.0, abs(float(ref)))
     if n_nodes:
         (3.0 * val).backward()
-        for p, o in zip(P, ops):
-            expect = o.grad if o.grad is not None else torch.zeros_like(o)
-            assert p.grad.shape == o.shape
-            assert torch.allclose(p.grad.cpu().double(), expect, rtol=2e-4, atol=1e-7)
+        for p, expect in zip(P, g_ref):
+            assert p.grad.shape == expect.shape
+            assert torch.allclose(p.grad.cpu().double(), 3.0 * expect, rtol=2e-4, atol=1e-7)
 
 
 @pytest.mark.parametrize("H,W,k,s", [(211, 333, 32, 16), (64, 96, 7, 7), (100, 100, 16, 5), (40, 40, 64, 16)])
@@ -246,8 +210,8 @@ def test_depth_ncc_loss_matches_the_reference_formulation(hip_lib, H, W, k, s):
     """mtgs_amd.loss.depth_ncc_loss against calculate_depth_ncc_loss (geometric_loss.py:322-348) restated with F.unfold in
     float64: value to 2e-5, gradient to 1e-3 of its maximum (fp32 sums over 1024-pixel patches); a 64-pixel patch on a
     40-pixel image has no valid patch: NaN, as the reference's mean of an empty tensor."""
-    import torch.nn.functional as F
     from mtgs_amd.loss import depth_ncc_loss
+    from tests.image_refs import depth_ncc_ref
     dev = torch.device("cuda")
     g = torch.Generator().manual_seed(H + k)
     gt = torch.rand(H, W, 1, generator=g) * 30 + 1
@@ -256,32 +220,16 @@ def test_depth_ncc_loss_matches_the_reference_formulation(hip_lib, H, W, k, s):
     mask = torch.rand(H, W, 1, generator=g) > 0.0005
     mask[: H // 8] = False
 
-    def reference(pred_depth, gt_depth, mask):
-        pred_depth, gt_depth = pred_depth.squeeze(-1), gt_depth.squeeze(-1)
-        pad = k // 2
-        m = mask.squeeze(-1).to(pred_depth.dtype)
-        pp = F.unfold(pred_depth[None, None], kernel_size=k, padding=pad, stride=s)
-        gp = F.unfold(gt_depth[None, None], kernel_size=k, padding=pad, stride=s)
-        mp = F.unfold(m[None, None], kernel_size=k, padding=pad, stride=s)
-        valid = mp.all(dim=1).squeeze(0)
-        pp, gp = pp[:, :, valid], gp[:, :, valid]
-        pc, gc = pp - pp.mean(dim=1, keepdim=True), gp - gp.mean(dim=1, keepdim=True)
-        ps = torch.sqrt((pc ** 2).mean(dim=1, keepdim=True) + 1e-8)
-        gs = torch.sqrt((gc ** 2).mean(dim=1, keepdim=True) + 1e-8)
-        return 1 - ((pc / ps) * (gc / gs)).mean(dim=1).mean(), int(valid.sum())
-
-    p_ref = pred0.double().requires_grad_(True)
-    ref, n_valid = reference(p_ref, gt.double(), mask)
+    ref, g_ref, n_valid = depth_ncc_ref(pred0, gt, mask, k, s)
     p = pred0.to(dev).requires_grad_(True)
     val = depth_ncc_loss(p, gt.to(dev), patch_size=k, stride=s, mask=mask.to(dev))
     if n_valid == 0:
         assert torch.isnan(val) and torch.isnan(ref)
         return
-    (2.0 * ref).backward()
     (2.0 * val).backward()
-    assert abs(float(val.detach()) - float(ref.detach())) <= 2e-5
-    scale = float(p_ref.grad.abs().max())
-    assert float((p.grad.cpu().double() - p_ref.grad).abs().max()) <= 1e-3 * scale
+    assert abs(float(val.detach()) - float(ref)) <= 2e-5
+    scale = float((2.0 * g_ref).abs().max())
+    assert float((p.grad.cpu().double() - 2.0 * g_ref).abs().max()) <= 1e-3 * scale
 
 
 @pytest.mark.parametrize("H,W,C_", [(97, 131, 3), (1, 50, 3), (40, 1, 1), (64, 64, 4)])
@@ -289,18 +237,17 @@ def test_tv_loss_matches_the_reference_formulation(hip_lib, H, W, C_):
     """mtgs_amd.loss.tv_loss against TVLoss.forward (geometric_loss.py:293-303) in float64; a one-pixel-wide image has an
     empty difference tensor whose mean is NaN in the reference too."""
     from mtgs_amd.loss import tv_loss
+    from tests.image_refs import tv_ref
     g = torch.Generator().manual_seed(H * 3 + W)
     x0 = torch.rand(H, W, C_, generator=g)
     if H > 5 and W > 5:
         x0[2, 3] = x0[2, 4]                       # exact ties: sign(0) = 0
-    xr = x0.double().requires_grad_(True)
-    ref = torch.mean(torch.abs(xr[:, :-1, :] - xr[:, 1:, :])) + torch.mean(torch.abs(xr[:-1, :, :] - xr[1:, :, :]))
+    ref, g_ref = tv_ref(x0)
     x = x0.cuda().requires_grad_(True)
     val = tv_loss(x)
     if torch.isnan(ref):
         assert torch.isnan(val)
         return
-    (1.5 * ref).backward()
     (1.5 * val).backward()
-    assert abs(float(val.detach()) - float(ref.detach())) < 2e-6
-    assert torch.allclose(x.grad.cpu().double(), xr.grad, rtol=1e-5, atol=1e-9)
+    assert abs(float(val.detach()) - float(ref)) < 2e-6
+    assert torch.allclose(x.grad.cpu().double(), 1.5 * g_ref, rtol=1e-5, atol=1e-9)

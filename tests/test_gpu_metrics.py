@@ -10,45 +10,11 @@ import numpy as np
 import pytest
 import torch
 
+from tests.image_refs import color_correct_ref as _cc_f64, depth_metrics_ref as _depth_ref, psnr_ref as _psnr
+
 pytestmark = pytest.mark.gpu
 
 GOLDEN = Path(__file__).resolve().parent / "golden" / "color_correct_ref.npz"
-EPS = 0.5 / 255
-LO, HI = float(np.float32(EPS)), float(np.float32(1 - EPS))
-
-
-def _features(x):
-    x0, x1, x2 = x[:, 0], x[:, 1], x[:, 2]
-    return np.stack([x0 * x0, x0 * x1, x0 * x2, x1 * x1, x1 * x2, x2 * x2, x0, x1, x2, np.ones_like(x0)], axis=1)
-
-
-def _cc_f64(img, ref, mask=None, iters=5):
-    """color_correct(img * mask, ref * mask) in float64: the algorithm of pnsr.py written from its description."""
-    img = img.reshape(-1, 3).astype(np.float64)
-    ref = ref.reshape(-1, 3).astype(np.float64)
-    if mask is not None:
-        m = mask.reshape(-1, 1).astype(np.float64)
-        img, ref = img * m, ref * m
-
-    def unclipped(z):
-        return (z >= LO) & (z <= HI)
-    m0 = unclipped(img)
-    x = img
-    for _ in range(iters):
-        a = _features(x)
-        w = np.zeros((10, 3))
-        for c in range(3):
-            sel = m0[:, c] & unclipped(x[:, c]) & unclipped(ref[:, c])
-            w[:, c] = np.linalg.lstsq(a[sel], ref[sel, c], rcond=None)[0]
-        x = np.clip(a @ w, 0, 1)
-    return x
-
-
-def _psnr(a, b, mask=None):
-    d = (a.reshape(-1, 3).astype(np.float64) - b.reshape(-1, 3).astype(np.float64)) ** 2
-    if mask is not None:
-        d = d[mask.reshape(-1)]
-    return 10 * np.log10(d.size / d.sum())
 
 
 def _structured(H, W, seed):
@@ -65,15 +31,6 @@ def _structured(H, W, seed):
     lidar = torch.where(torch.rand(H, W, 1, generator=g) > 0.7, 1 + 90 * torch.rand(H, W, 1, generator=g), torch.zeros(H, W, 1))
     depth = lidar * (1 + 0.3 * torch.randn(H, W, 1, generator=g)) + 0.5
     return pred, gt, mask, depth, lidar
-
-
-def _depth_ref(depth, lidar, mask):
-    """mtgs_scene_graph.py:788-798, in torch on the CPU (f32)"""
-    sel = (lidar > 0.1) & (lidar < 80) & mask
-    p, g = depth[sel], lidar[sel]
-    e = g - p
-    return (torch.sqrt((e.double() ** 2).mean()).item(), (e.abs() / g).double().mean().item(),
-            (torch.max(p / g, g / p) < 1.25).double().mean().item())
 
 
 def test_color_correct_matches_reference_golden():

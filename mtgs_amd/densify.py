@@ -202,7 +202,7 @@ def refine_gaussians(params: Dict[str, Tensor], stats: Tuple[Tensor, Tensor, Ten
          _C.c_uint64(seed & (2 ** 64 - 1)), int(step), ptr(src_index), ptr(kind), ptr(new["means"]), ptr(new["scales"]), st)
 
     if before_rows is not None and N > 0:
-        assert 1 <= S <= 5, S                      # (flag byte: bit 0 old row kept, bits 1..S children, bit 1+S duplicate, bit 7 split parent)
+        assert 1 <= S <= 4, S                      # (MAX_SAMPS of csrc/refine.hip; flag byte: bit 0 old row kept, bits 1..S children, bit 1+S duplicate, bit 7 split parent)
         before_rows((flags[:N] & (((1 << (S + 1)) - 1) << 1)) != 0)      # (bits 1 .. 1 + S: a child or the duplicate is kept)
 
     def rows(src, zero_new):

@@ -41,7 +41,9 @@ def quat_to_rotmat(q):
 
 def refinement_after(params, stats, cfg, step, normals, moments=None):
     """params: dict of float64 arrays with N rows; stats = (xys_grad_norm, vis_counts, max_2Dsize); cfg: an object with the
-    control fields; normals(index_array, slot) -> [n,3].  Returns (new_params, new_moments, masks)."""
+    control fields; normals(index_array, slot) -> [n,3].  Returns (new_params, new_moments, masks); masks["candidates"] holds
+    the means, scales and max_2Dsize of EVERY row of the concatenation [old | children | duplicates] the cull rules were
+    applied to (what a test needs to tell how far each cull decision was from its threshold)."""
     p = {k: np.array(v, dtype=np.float64) for k, v in params.items()}
     gn, vc, m2 = (np.asarray(t, dtype=np.float64).reshape(-1) for t in stats)
     N = p["means"].shape[0]
@@ -92,4 +94,5 @@ def refinement_after(params, stats, cfg, step, normals, moments=None):
         for k, (a, b) in moments.items():
             pad = lambda t: np.concatenate([np.asarray(t, np.float64), np.zeros((len(sp) * S + len(dp),) + t.shape[1:])], 0)[keep]
             new_m[k] = (pad(a), pad(b))
-    return new, new_m, {"splits": splits, "dups": dups, "keep": keep, "kind": kind[keep], "src_index": src[keep]}
+    return new, new_m, {"splits": splits, "dups": dups, "keep": keep, "kind": kind[keep], "src_index": src[keep],
+                        "candidates": {"means": allp["means"], "scales": allp["scales"], "max_2Dsize": m2_all}}

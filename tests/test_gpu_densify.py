@@ -7,19 +7,7 @@ import torch
 
 pytestmark = pytest.mark.gpu
 
-
-def _reference(stats, radii, xys_absgrad, submodel_mask, W, H):
-    """update_submodel_statistics + after_train for one node (tensors on CPU)."""
-    xys_grad_norm, vis_counts, max_2Dsize = stats
-    grads = xys_absgrad[0, submodel_mask].detach()
-    image_size = grads.new_tensor([W, H]).unsqueeze(0)
-    grads = (grads * image_size * 0.5).norm(dim=-1)
-    node_radii = radii[0, submodel_mask]
-    visible_mask = (node_radii > 0).flatten()
-    vis_counts[visible_mask] += +1
-    xys_grad_norm[visible_mask] += grads[visible_mask]
-    newradii = node_radii.detach()[visible_mask]
-    max_2Dsize[visible_mask] = torch.maximum(max_2Dsize[visible_mask], newradii)
+from tests.node_refs import stats_ref as _reference      # (update_submodel_statistics + after_train for one node, on the CPU)
 
 
 @pytest.mark.parametrize("sizes", [(5000,), (1200, 1, 3333, 64)])

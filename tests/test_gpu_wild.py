@@ -6,75 +6,15 @@
 (b) wild_color_source through rasterization() against wild_colors + rasterization(): bit-identical render and alpha (every row's
     colour is computed by the same code), gradients within (a)'s bound, and only the visible-row form of the kernels ran.
 (c) touch_first on and off, (d) bitwise-reproducible weight gradients, (e) one graph_mode capture + replay equals the eager step."""
-import numpy as np
 import pytest
 import torch
+
+from tests.row_refs import edge_dc as _edge_dc, wild_params as _params, wild_reference as _reference  # noqa: F401  (moved there)
 
 pytestmark = pytest.mark.gpu
 
 C0 = 0.28209479177387814
 NAMES = ("features_dc", "features_rest", "embedding", "w1", "b1", "w2", "b2", "w3", "b3")
-
-
-def _edge_dc():
-    """features_dc values whose fp32 dc * C0 + 0.5 is exactly 0 or exactly 1 (the clamp's edges), and their neighbours."""
-    c0 = np.float32(C0)
-    out = []
-    for target in (0.0, 1.0):
-        d = np.float32((target - 0.5) / C0)
-        for _ in range(64):
-            x = np.float32(np.float32(d * c0) + np.float32(0.5))
-            if x == target:
-                break
-            d = np.nextafter(d, np.float32(np.inf) if x < target else np.float32(-np.inf), dtype=np.float32)
-        assert np.float32(np.float32(d * c0) + np.float32(0.5)) == target
-        out += [d, np.nextafter(d, np.float32(np.inf), dtype=np.float32), np.nextafter(d, np.float32(-np.inf), dtype=np.float32)]
-    return torch.tensor(np.array(out, dtype=np.float32))
-
-
-def _params(N, seed=0, with_emb=True, dev="cuda"):
-    g = torch.Generator().manual_seed(seed)
-    dc = (torch.rand(N, 3, generator=g) - 0.5) * 1.2 / C0      # about a fifth of the channels beyond the clamp
-    if N >= 6:
-        e = _edge_dc()
-        dc.view(-1)[:e.numel()] = e[:min(e.numel(), 3 * N)]
-    rest = 0.3 * torch.randn(N, 15, 3, generator=g)
-    emb = torch.randn(32, generator=g) if with_emb else None
-    mlp = torch.nn.Sequential(torch.nn.Linear(59, 128), torch.nn.ReLU(), torch.nn.Linear(128, 128), torch.nn.ReLU(),
-                              torch.nn.Linear(128, 6))
-    torch.manual_seed(seed)
-    for m in mlp:
-        if isinstance(m, torch.nn.Linear):
-            torch.nn.init.uniform_(m.weight, -0.15, 0.15)
-            torch.nn.init.uniform_(m.bias, -0.1, 0.1)
-    with torch.no_grad():        # (so that the network's output is not lost under the 0.01)
-        mlp[4].weight.mul_(20.0)
-        mlp[4].bias.mul_(20.0)
-    ts = [dc, rest, emb, mlp[0].weight.detach(), mlp[0].bias.detach(), mlp[2].weight.detach(), mlp[2].bias.detach(),
-          mlp[4].weight.detach(), mlp[4].bias.detach()]
-    return [None if t is None else t.clone().to(dev).requires_grad_(True) for t in ts]
-
-
-def _reference(ts, kinks=None):
-    """float64 evaluation of the formula; the clamp's pass-through mask is taken from the fp32 pre-activation (inclusive edges,
-    as torch.clamp), which is what the fp32 kernel sees.  kinks (a list): receives the rows with a hidden pre-activation within
-    1e-5 of zero, where fp32 and float64 may take different sides of a ReLU."""
-    dc, rest, emb, w1, b1, w2, b2, w3, b3 = ts
-    N = dc.shape[0]
-    pre32 = (dc.detach() * torch.tensor(C0, dtype=torch.float32)) + 0.5
-    mask = (pre32 >= 0) & (pre32 <= 1)
-    pre = dc.double() * C0 + 0.5
-    rgb = torch.where(mask, pre, pre32.clamp(0, 1).double())
-    e = torch.zeros(32, dtype=torch.float64, device=dc.device) if emb is None else emb.double().reshape(32)
-    x = torch.cat([rgb, rest.double().reshape(N, 45)[:, :24], e.expand(N, 32)], dim=1)
-    z1 = x @ w1.double().T + b1.double()
-    h = torch.relu(z1)
-    z2 = h @ w2.double().T + b2.double()
-    h = torch.relu(z2)
-    if kinks is not None:
-        kinks.append(((z1.detach().abs() < 1e-5).any(1) | (z2.detach().abs() < 1e-5).any(1)))
-    y = 0.01 * (h @ w3.double().T + b3.double())
-    return rgb * (1 + y[:, 3:6]) + y[:, :3]
 
 
 def _grads(ts):

@@ -256,12 +256,18 @@ def call(name: str, *args) -> None:
         raise RuntimeError(f"{name} failed (code {rc}): {msg}")
 
 
-def workspace(name: str, *dims, device, dtype) -> torch.Tensor:
-    """The scratch tensor whose element count the size query `name` reports for `dims`: dtype torch.float32 for the
-    *_workspace_floats entry points, torch.uint8 for the *_workspace_bytes ones."""
+def size_query(name: str, *dims) -> int:
+    """What the size query `name` (a *_bytes / *_floats entry point) reports for `dims`."""
     n = C.c_size_t(0)
     call(name, *dims, C.byref(n))
-    return torch.empty(n.value, dtype=dtype, device=device)
+    return n.value
+
+
+def workspace(name: str, *dims, device, dtype, pad: int = 0) -> torch.Tensor:
+    """The scratch tensor whose element count the size query `name` reports for `dims`: dtype torch.float32 for the
+    *_workspace_floats entry points, torch.uint8 for the *_workspace_bytes ones.  `pad` more elements for a caller that
+    aligns the pointer itself."""
+    return torch.empty(size_query(name, *dims) + pad, dtype=dtype, device=device)
 
 
 def require_gpu(*tensors) -> None:

@@ -21,14 +21,14 @@ Two forms, both csrc/wild.hip (exact-f32 MFMA, weight gradients reduced in a fix
 """
 from __future__ import annotations
 
-import ctypes as C
 from typing import Optional
 
 import torch
 from torch import Tensor
 
 from . import wrapper
-from ._lib import ptr, require_gpu, stream_of
+from ._lib import ptr, require_gpu, stream_of, workspace
+from .nodes import ColorSourceDefaults
 
 N_FEAT, N_EMBED, N_HIDDEN, N_OUT = 27, 32, 128, 6
 _SHAPES = (("w1", (N_HIDDEN, N_FEAT + N_EMBED)), ("b1", (N_HIDDEN,)), ("w2", (N_HIDDEN, N_HIDDEN)), ("b2", (N_HIDDEN,)),
@@ -110,12 +110,10 @@ def _backward(prep, shapes, need, cap, vis_ids, totals, grad_ptr, grad_stride, s
     dw = [wz(s, dtype=torch.float32, device=dev) for _, s in _SHAPES]
     d_e = wz(N_EMBED, dtype=torch.float32, device=dev) if (e is not None and need[2]) else None
     if cap > 0:
-        nbytes = C.c_size_t(0)
-        wrapper.call("mtgs_wild_workspace_bytes", cap, C.byref(nbytes))
-        part = torch.empty(nbytes.value // 4, dtype=torch.float32, device=dev)
+        part = workspace("mtgs_wild_workspace_bytes", cap, device=dev, dtype=torch.uint8)
         wrapper.call("mtgs_wild_bwd", cap, ptr(vis_ids), ptr(totals), grad_ptr, grad_stride, ptr(dc2), dc2.stride(0), ptr(rest2),
                      rest2.stride(0), ptr(e), ptr(w1), ptr(b1), ptr(w2), ptr(b2), ptr(w3), ptr(b3), *_widths(), ptr(d_dc),
-                     ptr(d_rest), R3, ptr(part), nbytes.value, st)
+                     ptr(d_rest), R3, ptr(part), part.numel(), st)
         wrapper.call("mtgs_wild_reduce", cap, ptr(part), ptr(e), ptr(w1), *_widths(), *(ptr(t) for t in dw), ptr(d_e), st)
     grads = [d_dc.view(shapes[0]), d_rest.view(shapes[1]), None if d_e is None else d_e.view(shapes[2])] + dw
     return tuple(g if n else None for g, n in zip(grads, need))
@@ -151,7 +149,7 @@ def wild_colors(features_dc: Tensor, features_rest: Tensor, embedding: Optional[
     return _WildColors.apply(features_dc, features_rest, embedding, *ws)
 
 
-class WildColorSource:
+class WildColorSource(ColorSourceDefaults):
     """Colour source for rasterization(color_source=...): channels 0..2 of the blended colours are the appearance colours of the
     VISIBLE Gaussians, evaluated by the rasterization between its front end and its binning (csrc/wild.hip, visible-row form),
     and its backward turns the colour-gradient rows of the compositing backward into dense gradients of the nine inputs, which
@@ -161,13 +159,6 @@ class WildColorSource:
     exchange: the rasterization refuses the others by name."""
 
     wild = True
-    autograd = False          # (the attributes the rasterization reads from a nodes.ColorSource)
-    exchange = False
-    geometry_rows = False
-    want_grad_rows = False
-    dirs = None
-    dirs_inputs = None
-    n_nodes = 1
 
     def __init__(self, features_dc, features_rest, embedding, ws, camera_normals=None, touch_first=False):
         self.wild_inputs = (features_dc, features_rest, embedding) + tuple(ws)

@@ -167,6 +167,8 @@ class SparseGradExchange:
     degree > 3) take the per-sender read-modify-write path (mtgs_dp_pack / mtgs_dp_accumulate)."""
 
     ROW = 16
+    rows_hook = None        # what the rasterization reads besides rows / front_pointers(): see __init__
+    zero_region = None
 
     def __init__(self, n_gaussians: int, n_sh_bases: int, device, group=None, chunks: int = 4, traversals: int = 1):
         self.N, self.K, self.device, self.group = int(n_gaussians), int(n_sh_bases), device, group

@@ -169,7 +169,28 @@ def upload_table(tab: np.ndarray, dev) -> Tensor:
     return staged.to(dev, non_blocking=True)
 
 
-class ColorSource:
+class ColorSourceDefaults:
+    """What the rasterization (wrapper._FusedRasterization) reads from ANY colour source, with the value that means "not this kind
+    of source"; a source sets what it supports."""
+    wild = False               # appearance.WildColorSource: colour_rows() / backward_rows() instead of the SH colour kernels
+    exchange = False           # the colours of a data-parallel frame: their gradient travels in the exchange's wire rows
+    autograd = False           # the coefficient gradient leaves the rasterization as dense autograd tensors
+    geometry_rows = False      # the geometry gradient stays in per-visible rows
+    want_grad_rows = False     # the 2-D gradients stay in the compact rows: no dense absgrad
+    touch_first = False        # colours only for the Gaussians the frame composites from
+    camera_normals = None      # camera_to_world [3, 4]: three camera-space normal channels follow the colours
+    dirs = None                # the caller's view directions [N, 3]
+    dirs_inputs = None         # ... as inputs of the autograd node, when they carry a gradient
+    wild_inputs = None         # the nine inputs of a WildColorSource, as inputs of the autograd node
+    n_nodes = 1
+
+    @property
+    def open_channels(self) -> int:
+        """Blended channels the source fills for the visible Gaussians: 3 colours, + 3 with camera_normals."""
+        return 6 if self.camera_normals is not None else 3
+
+
+class ColorSource(ColorSourceDefaults):
     """Visibility-first colours (collect_gaussians(..., deferred_colors=True) -> rasterization(..., color_source=...)).
 
     Holds the node table (csrc/viscolor.hip reads the SH coefficients of the VISIBLE Gaussians through it), and after the

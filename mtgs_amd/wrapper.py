@@ -17,7 +17,7 @@ import contextlib
 import threading
 import time
 import weakref
-from typing import Optional, Tuple
+from typing import NamedTuple, Optional, Tuple
 
 import torch
 from torch import Tensor
@@ -587,12 +587,6 @@ def _bit_length(v: int) -> int:
     return int(v).bit_length()
 
 
-def _ws(nbytes_fn: str, n: int, dev) -> Tuple[Tensor, int]:
-    nbytes = C.c_size_t(0)
-    call(nbytes_fn, n, C.byref(nbytes))
-    return torch.empty(nbytes.value, dtype=torch.uint8, device=dev), nbytes.value
-
-
 @torch.no_grad()
 def isect_tiles(means2d: Tensor, radii: Tensor, depths: Tensor, tile_size: int, tile_width: int,
                 tile_height: int, sort: bool = True, packed: bool = False,
@@ -619,11 +613,11 @@ def isect_tiles(means2d: Tensor, radii: Tensor, depths: Tensor, tile_size: int, 
     tiles_per_gauss = torch.empty((Cn, N), dtype=torch.int32, device=dev)
     call("mtgs_isect_count", Cn, N, ptr(means2d), ptr(radii), tile_size, tile_width, tile_height,
          ptr(tiles_per_gauss), st)
-    scan_ws, scan_bytes = _ws("mtgs_scan_workspace_bytes", total, dev)
+    scan_ws = _lib.workspace("mtgs_scan_workspace_bytes", total, device=dev, dtype=torch.uint8)
     if not sort:
         cum = torch.empty(max(total, 1), dtype=torch.int64, device=dev)
         m_dev = torch.empty(1, dtype=torch.int64, device=dev)
-        call("mtgs_isect_scan", total, ptr(tiles_per_gauss), ptr(cum), ptr(m_dev), ptr(scan_ws), scan_bytes, st)
+        call("mtgs_isect_scan", total, ptr(tiles_per_gauss), ptr(cum), ptr(m_dev), ptr(scan_ws), scan_ws.numel(), st)
         M = int(m_dev.item())  # the one host sync of a frame (gsplat does the same)
         isect_ids = torch.empty(M, dtype=torch.int64, device=dev)
         flatten_ids = torch.empty(M, dtype=torch.int32, device=dev)
@@ -632,8 +626,7 @@ def isect_tiles(means2d: Tensor, radii: Tensor, depths: Tensor, tile_size: int, 
                  tile_width, tile_height, ptr(isect_ids), ptr(flatten_ids), st)
         return tiles_per_gauss, isect_ids, flatten_ids
 
-    return _bin_depth_ordered(means2d, radii, depths, tiles_per_gauss, scan_ws, scan_bytes, tile_size, tile_width,
-                              tile_height)[:3]
+    return _bin_depth_ordered(means2d, radii, depths, tiles_per_gauss, scan_ws, tile_size, tile_width, tile_height)[:3]
 
 
 _mailboxes = threading.local()
@@ -678,7 +671,7 @@ def _wait_mailbox(mailbox, tag, device_totals, limit: int) -> Tuple[int, int]:
     return n_vis, M
 
 
-def _bin_depth_ordered(means2d, radii, depths, tiles_per_gauss, scan_ws, scan_bytes, tile_size, tile_width, tile_height,
+def _bin_depth_ordered(means2d, radii, depths, tiles_per_gauss, scan_ws, tile_size, tile_width, tile_height,
                        want_rank: bool = False):
     """Depth-ordered binning (csrc/bin.hip) after mtgs_isect_count.  Returns (tiles_per_gauss, isect_ids,
     flatten_ids, offsets, tile_order, vis_ids[n_vis], vis_rank[C*N] | None)."""
@@ -691,7 +684,7 @@ def _bin_depth_ordered(means2d, radii, depths, tiles_per_gauss, scan_ws, scan_by
     totals = torch.empty(1, dtype=torch.int64, device=dev)
     mailbox, tag = _host_mailbox()
     call("mtgs_bin_compact", Cn, N, ptr(radii), ptr(depths), ptr(tiles_per_gauss), ptr(vis_keys),
-         ptr(vis_ids), ptr(vis_rank), ptr(totals), mailbox.data_ptr(), tag, ptr(scan_ws), scan_bytes, st)
+         ptr(vis_ids), ptr(vis_rank), ptr(totals), mailbox.data_ptr(), tag, ptr(scan_ws), scan_ws.numel(), st)
     # the one host round trip of a frame: n_vis and M together.  The kernel publishes them to pinned host memory as
     # soon as they are known (one kernel before the compaction ends); polling that word instead of synchronising the
     # stream lets the host enqueue the rest of the frame while the GPU is still busy (27 us per frame otherwise).
@@ -704,12 +697,10 @@ def _bin_depth_ordered(means2d, radii, depths, tiles_per_gauss, scan_ws, scan_by
     # rasterize_to_pixels instead of being recomputed).
     offsets = torch.empty((Cn, tile_height, tile_width), dtype=torch.int32, device=dev)
     order = torch.empty(Cn * tile_height * tile_width, dtype=torch.int32, device=dev)
-    nbytes = C.c_size_t(0)
-    call("mtgs_bin_workspace_bytes", n_vis, M, C.byref(nbytes))
-    bin_ws = torch.empty(nbytes.value, dtype=torch.uint8, device=dev)
+    bin_ws = _lib.workspace("mtgs_bin_workspace_bytes", n_vis, M, device=dev, dtype=torch.uint8)
     call("mtgs_bin_build", Cn, N, n_vis, M, ptr(means2d), ptr(radii), ptr(depths), ptr(tiles_per_gauss),
          ptr(vis_keys), ptr(vis_ids), tile_size, tile_width, tile_height, ptr(isect_ids), ptr(flatten_ids),
-         ptr(offsets), ptr(order), ptr(bin_ws), nbytes.value, st)
+         ptr(offsets), ptr(order), ptr(bin_ws), bin_ws.numel(), st)
     offsets._mtgs_tile_order = order
     isect_ids._mtgs_offsets = offsets
     return tiles_per_gauss, isect_ids, flatten_ids, offsets, order, vis_ids[:n_vis], vis_rank
@@ -730,6 +721,12 @@ def isect_offset_encode(isect_ids: Tensor, n_cameras: int, tile_width: int, tile
 
 
 # ------------------------------------------------------------------------------------- compositing
+def _row_stride(DT: int) -> int:
+    """Floats of a gradient row [xy 2 | |xy| 2 | conic 3 | opacity 1 | DT blended channels | pad]: whole 64-byte lines
+    (16 floats for <= 8 channels)."""
+    return -(-(8 + DT) // 16) * 16
+
+
 class _RasterizeToPixels(torch.autograd.Function):
     """rasterize_to_pixels, optionally fused with the depth channel (`depths` blended as the last
     channel instead of torch.cat) and the expected-depth normalisation (`ed`) that gsplat's
@@ -774,12 +771,11 @@ class _RasterizeToPixels(torch.autograd.Function):
         CN = Cn * N
         v_render, v_alphas = _f32c(v_render), _f32c(v_alphas)
         # ONE zero-filled, interleaved buffer for every atomically accumulated gradient: rows of RS floats
-        #   [xy 2 | |xy| 2 | conic 3 | opacity 1 | colour DC | depth 1 | pad]   (RS = 16 for <= 8 channels)
+        #   [xy 2 | |xy| 2 | conic 3 | opacity 1 | colour DC | depth 1 | pad]   (_row_stride)
         # so that the 12 atomics of a (tile, Gaussian) entry land in one 64-byte line (5x cheaper than six
         # dense arrays, include/mtgs_rast.h); the gradients handed to autograd are views of it, which the
         # projection backward reads in place (_strided_rows).
-        DT = DC + (1 if dep is not None else 0)
-        RS = -(-(8 + DT) // 16) * 16
+        RS = _row_stride(DC + (1 if dep is not None else 0))
         G = torch.zeros((Cn, N, RS), dtype=torch.float32, device=m2d.device)
         v_means2d, v_abs_buf, v_conics, v_opacities = G[..., 0:2], G[..., 2:4], G[..., 4:7], G[..., 7]
         v_colors = G[..., 8:8 + DC] if DC else None
@@ -799,6 +795,7 @@ class _RasterizeToPixels(torch.autograd.Function):
 
 
 # ------------------------------------------------------------------------------------- fused path
+TILE_SIZE = 16           # the tile edge of the fused path (pixels)
 RECORD_CHANNELS = 8      # blended channels a packed record holds (csrc/raster_rec.hpp)
 speculative_sizing = True  # enqueue binning + compositing before the host knows (n_vis, M); see _SizePlan
 _force_caps = None       # tests: (cap_vis, cap_M) used for the speculative attempt, to exercise the overflow path
@@ -949,6 +946,251 @@ def _bin3_ok(Cn, tw, th, cap_M) -> bool:
     return bool(_lib.load().mtgs_bin3_supported(Cn, tw, th, cap_M))
 
 
+def _open_channels(cs) -> int:
+    """Blended channels a colour source fills for the visible Gaussians (0 without a source; see ColorSourceDefaults.open_channels)."""
+    return 0 if cs is None else cs.open_channels
+
+
+def _gather_path(ins, dims, outs):
+    """The gather-based kernels (csrc/project.hip, bin.hip, blend.hip with dense attribute arrays) for a frame outside the packed
+    path's limits; arguments and result as _packed_path's."""
+    means, quats, scales, opacities, col, viewmats, Ks, bg = ins
+    Cn, N, width, height, tw, th, DC, with_depth, ed, eps2d, near_plane, far_plane, radius_clip = dims
+    radii, means2d, depths, conics, comps, opac_eff, tiles_per_gauss, render, alphas, last_ids = outs
+    st = stream_of(means)
+    call("mtgs_project_fwd", Cn, N, ptr(means), ptr(quats), ptr(scales), ptr(viewmats), ptr(Ks),
+         width, height, eps2d, near_plane, far_plane, radius_clip, ptr(opacities), ptr(radii),
+         ptr(means2d), ptr(depths), ptr(conics), ptr(comps), ptr(opac_eff), TILE_SIZE, tw, th,
+         ptr(tiles_per_gauss), st)     # (+ the count pass of isect_tiles)
+    scan_ws = _lib.workspace("mtgs_scan_workspace_bytes", Cn * N, device=means.device, dtype=torch.uint8)
+    _, isect_ids, flatten_ids, offsets, order, vis_ids, vis_rank = _bin_depth_ordered(
+        means2d, radii, depths, tiles_per_gauss, scan_ws, TILE_SIZE, tw, th, want_rank=True)
+    dep = depths if with_depth else None
+    call("mtgs_blend_fwd", Cn, N, DC, ptr(means2d), ptr(conics), ptr(col), ptr(opac_eff), ptr(bg), ptr(dep), int(ed),
+         width, height, TILE_SIZE, tw, th, ptr(offsets), ptr(flatten_ids), flatten_ids.numel(), ptr(render),
+         ptr(alphas), ptr(last_ids), ptr(order), st)
+    totals = torch.zeros(1, dtype=torch.int64, device=means.device)
+    return isect_ids, flatten_ids, offsets, offsets, order, vis_ids, vis_rank, totals, None, None, None, 0, None, None
+
+
+class _Front:
+    """What mtgs_front_fwd fills for a capacity of visible Gaussians: their packed records, ids and depth keys, the colour kernel's
+    mask (with a colour source), and the mailbox their count arrives in."""
+    __slots__ = ("recs", "vis_ids", "vis_keys", "vis_mask", "cap_vis", "mailbox", "tag")
+
+    def __init__(self, cap_vis, dev, with_mask):
+        self.recs = torch.empty((cap_vis, 16), dtype=torch.float32, device=dev)
+        self.vis_ids = torch.empty(cap_vis, dtype=torch.int32, device=dev)
+        self.vis_keys = torch.empty(cap_vis, dtype=torch.int64, device=dev)
+        self.vis_mask = torch.empty(cap_vis, dtype=torch.uint8, device=dev) if with_mask else None
+        self.cap_vis = cap_vis
+
+
+class _TileLists(NamedTuple):
+    """The per-tile lists mtgs_bin3_build fills for a capacity of intersections."""
+    rank_ids: Tensor
+    flatten_ids: Tensor
+    isect_ids: Tensor
+
+
+def _packed_path(ins, dims, outs, need, dp, cs):
+    """Packed records (csrc/front.hip, bin3.hip, blend.hip).  ins, dims, outs: the inputs, sizes and allocated outputs of
+    _FusedRasterization.forward; need: its needs_input_grad.  Returns (isect_ids, flatten_ids, offsets, the offsets the backward
+    reads, order, vis_ids, vis_rank, totals, recs, rank_ids, vis_mask, cap_vis, zero_rows, zero_coeffs)."""
+    means, quats, scales, opacities, col, viewmats, Ks, bg = ins
+    Cn, N, width, height, tw, th, DC, with_depth, ed, eps2d, near_plane, far_plane, radius_clip = dims
+    radii, means2d, depths, conics, comps, opac_eff, tiles_per_gauss, render, alphas, last_ids = outs
+    dev, st = means.device, stream_of(means)
+    n2c = None if cs is None else cs.camera_normals      # [3,4] camera_to_world: three normal channels
+    zero_rows = zero_coeffs = None      # gradient rows / dense coefficient gradient that the compositing kernel clears for the backward
+    total = Cn * N
+    key = (Cn, N, width, height)
+    front_ws = _lib.workspace("mtgs_front_workspace_bytes", total, device=dev, dtype=torch.uint8)
+    graph_caps = _graph.caps
+    # (graph mode: {packed, n_vis, M, overflow} -- words 1..3 are written by the binning, MTGS_BIN3_STATUS)
+    totals = torch.empty(4 if graph_caps is not None else 1, dtype=torch.int64, device=dev)
+    vis_rank = torch.empty(total, dtype=torch.int32, device=dev)
+    offsets_buf = torch.empty(Cn * th * tw + 1, dtype=torch.int32, device=dev)
+    order = torch.empty(Cn * th * tw, dtype=torch.int32, device=dev)
+    if graph_caps is not None and _graph.owner != threading.get_ident():
+        raise RuntimeError("rasterization(): mtgs_amd.graph_mode is active on another thread (fixed capacities, no host "
+                           "read-back); serialise the two callers or leave graph_mode first")
+
+    # TOUCH FIRST (ColorSource.touch_first, opt-in): the binning needs the records' geometry only, so it runs in front of the
+    # colours, and one pass of the compositing DECISIONS (mtgs_blend_touch_packed) flags the Gaussians the frame composites
+    # from -- a few percent of the visible ones in an opaque scene.  Peek, SH evaluation and normals work on those alone.
+    touch_first = cs is not None and bool(cs.touch_first)
+    # tile lists of this frame (thread-local mode, read once): gsplat's by default; mtgs_bin3_build flags: 1 = tight lists,
+    # 2 = sentinel-fill the tail [n_listed, M) of flatten_ids / isect_ids (tight lists, tensors sliced to gsplat's M),
+    # 4 = sentinel-fill up to the capacity (graph mode: the tensors are capacity-sized in both list modes), 16 = the frame's
+    # counts and its overflow flag as device words behind `totals` (graph mode)
+    tight = lists_are_tight()
+    list_flags = (1 if tight else 0) | (4 | 16 if graph_caps is not None else (2 if tight else 0))
+
+    def colours(b, flags):   # colours of the visible Gaussians, straight into their records
+        cap_vis = b.cap_vis
+        if cs.wild:          # WildGaussians appearance colours (appearance.WildColorSource, csrc/wild.hip)
+            cs.colour_rows(b.vis_ids, totals, cap_vis, b.recs, flags, st)
+        else:
+            coef = cs.prepare(vis_rank, cap_vis, b.vis_ids, totals, row_flags=flags)    # (row-lazy optimizer: up-to-date coefficient rows, compact)
+            call("mtgs_vis_color_fwd_dirs", cs.n_nodes, ptr(cs.table), cs.degree, ptr(cs.cam), ptr(means), ptr(b.vis_ids),
+                 ptr(totals), cap_vis, ptr(b.recs), ptr(b.vis_mask), ptr(coef), 0 if coef is None else coef.stride(0),
+                 ptr(flags), ptr(cs.dirs), st)
+        if n2c is not None:  # ... and their camera-space normals (channels 3..5)
+            call("mtgs_normals_fwd_rows", cap_vis, ptr(b.vis_ids), ptr(totals), ptr(quats), ptr(scales), ptr(means),
+                 ptr(n2c), ptr(b.recs), 3, ptr(flags), st)
+
+    def bin_ws(cap_vis, cap_M):      # the binning's workspace, 256-byte aligned: (tensor, pointer, bytes, bytes of its control words)
+        ws = _lib.workspace("mtgs_bin3_workspace_bytes", Cn, tw, th, cap_vis, cap_M, device=dev, dtype=torch.uint8, pad=256)
+        return ws, ws.data_ptr() + (-ws.data_ptr()) % 256, ws.numel() - 256, _lib.size_query("mtgs_bin3_control_bytes", Cn, tw, th)
+
+    def front(cap_vis, repeat=False, prezero=None):
+        # prezero = bin_ws(...) of the binning that follows: its control words are cleared by the compaction kernel here
+        # repeat=True: the capacity-overflow repeat of a frame.  The visibility map / row count of the exchange do not
+        # depend on cap_vis and are already on their way: they are neither rewritten nor gathered a second time
+        # (a second meta all-gather on ONE rank would desynchronise the ranks' collectives).
+        dpf = dp if not repeat else None
+        b = _Front(cap_vis, dev, cs is not None)
+        mailbox, tag = _host_mailbox() if graph_caps is None else (None, 0)
+        call("mtgs_front_fwd", Cn, N, ptr(means), ptr(quats), ptr(scales), ptr(viewmats), ptr(Ks), width, height,
+             eps2d, near_plane, far_plane, radius_clip, ptr(opacities), ptr(col), DC, with_depth, ptr(radii),
+             ptr(means2d), ptr(depths), ptr(conics), ptr(comps), ptr(opac_eff), TILE_SIZE, tw, th,
+             ptr(tiles_per_gauss), ptr(b.recs), ptr(b.vis_ids), ptr(b.vis_keys),
+             ptr(vis_rank), cap_vis, *(dpf.front_pointers() if dpf is not None else (None, None, None)),
+             (1 if dp is not None else 0) if cs is None else (3 if n2c is not None else 2), ptr(totals),
+             None if mailbox is None else mailbox.data_ptr(), tag,
+             None if prezero is None else prezero[1], 0 if prezero is None else prezero[3],
+             ptr(front_ws), front_ws.numel(), st)
+        if cs is not None and not touch_first:
+            colours(b, None)
+        b.mailbox, b.tag = mailbox, tag
+        if dpf is not None:
+            dpf.after_front()      # the visibility maps travel while this frame is composited
+        return b
+
+    def rest(b, cap_M, prezeroed=None):
+        nonlocal zero_rows, zero_coeffs
+        cap_alloc = max(cap_M, 1)
+        out = _TileLists(torch.empty(cap_alloc, dtype=torch.int32, device=dev), torch.empty(cap_alloc, dtype=torch.int32, device=dev),
+                         torch.empty(cap_alloc, dtype=torch.int64, device=dev))
+        ws, ws_ptr, ws_bytes, _ = prezeroed if prezeroed is not None else bin_ws(b.cap_vis, cap_M)
+        call("mtgs_bin3_build", Cn, N, TILE_SIZE, tw, th, ptr(totals), b.cap_vis, cap_M, ptr(b.recs),
+             ptr(b.vis_ids), ptr(b.vis_keys), ptr(out.rank_ids),
+             ptr(out.flatten_ids), ptr(out.isect_ids), ptr(offsets_buf), ptr(order),
+             list_flags | (8 if prezeroed is not None else 0), ws_ptr, ws_bytes, st)
+        if touch_first:
+            flags = torch.empty(max(b.cap_vis, 1), dtype=torch.uint8, device=dev)
+            call("mtgs_blend_touch_packed", Cn, ptr(b.recs), width, height, tw, th, ptr(offsets_buf), ptr(out.rank_ids),
+                 ptr(order), ptr(flags), b.cap_vis, st)
+            colours(b, flags)
+        # a training forward: its compositing kernel (VALU-bound, HBM mostly idle) clears what the backward pass will want
+        # zeroed -- the gradient rows of the compositing backward, the dL/dcoeffs of the SH backwards (_Prefill)
+        z_ptr, z_bytes = None, 0
+        if _prefill.enabled and _prefill.in_forward and any(need) and dp is None and zero_rows is None:
+            RS = _row_stride(DC + with_depth)
+            n_rows = max(b.cap_vis, 1) * RS
+            # (gsplat's sh_degree call style: the dense [N, 16, 3] coefficient gradient too -- the backward then writes the
+            #  rows of the Gaussians with a cotangent straight into it, mtgs_vis_color_bwd(dense_rows))
+            n_coef = N * 48 if (cs is not None and cs.autograd and cs.width == 48 and (cs.n_nodes == 1 or cs.dirs is not None)
+                                and (graph_caps is None or cs.dirs is not None) and _needs_coeffs(need, cs)) else 0
+            z_ptr, z_bytes, own = _prefill.take(dev, n_rows + n_coef, only=getattr(_sh_scope, "reqs", ()))
+            zero_rows = own[:n_rows].view(max(b.cap_vis, 1), RS)
+            if n_coef:
+                zero_coeffs = own[n_rows:].view(N, 16, 3)
+        elif dp is not None and dp.zero_region is not None and any(need):
+            # data-parallel frame: the dense sums the exchange will return (SparseGradExchange.prezero) are cleared here too
+            z_ptr, z_bytes = dp.zero_region
+        call("mtgs_blend_fwd_packed", Cn, DC, with_depth, ptr(b.recs), ptr(bg), int(ed), width, height, tw, th,
+             ptr(offsets_buf), ptr(out.rank_ids), ptr(render), ptr(alphas), ptr(last_ids), ptr(order), z_ptr, z_bytes, st)
+        return out
+
+    caps = _force_caps or (_size_plan.caps(key, total) if speculative_sizing else None)
+    if caps is not None and not _bin3_ok(Cn, tw, th, caps[1]):
+        caps = None
+    if graph_caps is not None:
+        # graph mode: fixed capacities, nothing waits for the host; the counts stay on the device
+        if dp is not None or not _bin3_ok(Cn, tw, th, graph_caps[1]):
+            raise NotImplementedError("graph_mode: unsupported configuration (data-parallel exchange / capacity >= 2^30)")
+        pz = bin_ws(min(graph_caps[0], total), graph_caps[1])
+        b = front(min(graph_caps[0], total), prezero=pz)
+        out = rest(b, graph_caps[1], prezeroed=pz)
+        n_vis, M = b.cap_vis, graph_caps[1]
+    elif caps is not None:
+        # speculative capacities: everything is enqueued before the totals are known
+        pz = bin_ws(min(caps[0], total), caps[1])
+        b = front(min(caps[0], total), prezero=pz)
+        out = rest(b, caps[1], prezeroed=pz)
+        n_vis, M = _wait_mailbox(b.mailbox, b.tag, totals, total)
+        if n_vis > b.cap_vis or M > caps[1]:   # capacities too small: repeat with exact sizes
+            if not _bin3_ok(Cn, tw, th, M):
+                raise NotImplementedError(f"rasterization: {M} tile intersections in one call (limit 2^30)")
+            if n_vis > b.cap_vis:
+                b = front(n_vis, repeat=True)
+            out = rest(b, M)
+    else:
+        # exact sizes: the binning waits for the front kernel's totals
+        b = front(total)
+        n_vis, M = _wait_mailbox(b.mailbox, b.tag, totals, total)
+        if not _bin3_ok(Cn, tw, th, M):
+            raise NotImplementedError(f"rasterization: {M} tile intersections in one call (limit 2^30)")
+        b.cap_vis = max(n_vis, 0)              # (buffers are larger; the kernels only need a bound)
+        out = rest(b, M)
+    if graph_caps is None:
+        _size_plan.update(key, n_vis, M)
+    isect_ids = out.isect_ids[:M]
+    offsets = offsets_buf[:Cn * th * tw].view(Cn, th, tw)
+    offsets._mtgs_tile_order = order
+    if tight or graph_caps is not None:
+        offsets._mtgs_n_listed = offsets_buf[Cn * th * tw]     # (device scalar: the number of pairs in the lists)
+    isect_ids._mtgs_offsets = offsets
+    return (isect_ids, out.flatten_ids[:M], offsets, offsets_buf, order, b.vis_ids[:n_vis], vis_rank, totals, b.recs, out.rank_ids[:M],
+            b.vis_mask, b.cap_vis, zero_rows, zero_coeffs)
+
+
+class _BackwardPlan(NamedTuple):
+    """What one _FusedRasterization backward returns and where it writes it (see _backward_plan)."""
+    want_m2d: bool      # means2d.grad (the caller's retain_grad())
+    want_abs: bool      # means2d.absgrad, dense
+    want_col: bool      # the dense gradient of the colour channels the caller gave
+    c0: int             # ... which are the channels from c0 on (those before are the colour source's)
+    rows_only: bool     # the caller takes the 2-D gradients from the compact rows: no dense absgrad
+    geo_rows: bool      # the per-visible rows ARE the geometry gradient: no dense v_means / v_quats / v_scales / v_opacities
+    zeroed: bool        # the dense gradients are views of ONE region that the compositing backward clears (mtgs_project_bwd_zeroed)
+    floats: int         # ... its size, and {name: (offset, count, shape)}, every view 16-byte aligned (both empty unless zeroed)
+    views: dict
+
+
+def _backward_plan(*, packed, Cn, N, n_vis, DC, absgrad, has_dp, info_grads, m2d_alive, m2d_retains, need_colors, open_channels,
+                   geometry_rows, want_grad_rows, prefill_enabled, zeroed_outputs) -> _BackwardPlan:
+    """The decisions of a _FusedRasterization backward, taken ONCE from plain values (no tensors, no GPU) in front of its compositing
+    kernel, because that kernel clears the region the dense gradients are views of.
+    packed: the packed compositing backward runs (packed records, a non-empty tile list, a cotangent on render or alphas);
+    has_dp: a data-parallel exchange takes the gradients; info_grads: a gradient arrived on an info[...] tensor; m2d_alive /
+    m2d_retains: the caller still holds info["means2d"] / called retain_grad() on it; need_colors: `colors` needs a gradient;
+    open_channels, geometry_rows, want_grad_rows: the colour source's (0, False, False without one); prefill_enabled,
+    zeroed_outputs: the switches _prefill.enabled and _zeroed_outputs."""
+    rows_only, c0 = bool(want_grad_rows), open_channels
+    want_m2d = bool(m2d_alive and m2d_retains)
+    want_abs = bool(absgrad and m2d_alive and not rows_only)
+    want_col = bool(DC > c0 and need_colors)
+    geo_rows = bool(geometry_rows and not info_grads and n_vis > 0)
+    zeroed = bool(prefill_enabled and zeroed_outputs and packed and Cn == 1 and not has_dp and n_vis > 0 and N > 0
+                  and not info_grads and not geometry_rows)
+    views, at = {}, 0
+    if zeroed:
+        items = [("means", N * 3, (N, 3)), ("quats", N * 4, (N, 4)), ("scales", N * 3, (N, 3)), ("opacities", N, (N,))]
+        if want_m2d:
+            items.append(("m2d", N * 2, (1, N, 2)))
+        if want_abs:
+            items.append(("abs", N * 2, (1, N, 2)))
+        if want_col:
+            items.append(("col", N * (DC - c0), (1, N, DC - c0)))
+        for name, n_, shape in items:
+            views[name] = (at, n_, shape)
+            at += -(-n_ // 4) * 4
+    return _BackwardPlan(want_m2d, want_abs, want_col, c0, rows_only, geo_rows, zeroed, at, views)
+
+
 class _FusedRasterization(torch.autograd.Function):
     """projection -> tile binning -> compositing as ONE autograd node: what gsplat.rendering.rasterization
     chains from fully_fused_projection / isect_tiles / rasterize_to_pixels (same results).
@@ -976,22 +1218,25 @@ class _FusedRasterization(torch.autograd.Function):
         channels ([C,N,DX] or None); the backward leaves the coefficient gradient as compact rows in `cs` (rows, row_of).
         sh_coeffs [N,K,3], campos [3] (with cs.autograd): gsplat's own `sh_degree` call style -- the coefficient gradient is
         expanded to a dense tensor for autograd, and the view directions are differentiable (means, camera position).
-        sh_more (with cs.dirs, sh_direction_source): the coefficient tensors of the further nodes, in collected order -- node i's
-        gradient is the slice [start_i, start_i + n_i) of the dense one --, then (cs.dirs_inputs) every node's direction tensor when
-        the directions carry a gradient: theirs is the slice of a dense [N, 3] one."""
+        sh_more (see _tail_inputs): with cs.dirs (sh_direction_source) the coefficient tensors of the further nodes, in collected
+        order -- node i's gradient is the slice [start_i, start_i + n_i) of the dense one --, then (cs.dirs_inputs) every node's
+        direction tensor when the directions carry a gradient: theirs is the slice of a dense [N, 3] one; or the nine cs.wild_inputs."""
+        # ---- validate
         require_gpu(means, quats, scales, opacities, colors, viewmats, Ks, backgrounds)
-        means, quats, scales, opacities, col, viewmats, Ks, bg = map(
-            _f32c, (means, quats, scales, opacities, colors, viewmats, Ks, backgrounds))
+        ins = means, quats, scales, opacities, col, viewmats, Ks, bg = tuple(map(
+            _f32c, (means, quats, scales, opacities, colors, viewmats, Ks, backgrounds)))
         N, Cn = means.shape[0], viewmats.shape[0]
-        dev, st = means.device, stream_of(means)
-        tile_size = 16
-        tw, th = -(-width // tile_size), -(-height // tile_size)
-        n2c = getattr(cs, "camera_normals", None) if cs is not None else None     # [3,4] camera_to_world: three normal channels
-        c_open = 0 if cs is None else (6 if n2c is not None else 3)                 # channels filled for the visible Gaussians
-        DC = (0 if col is None else col.shape[-1]) + c_open
-        DT = DC + int(with_depth)
-        ed = bool(expected_depth)
-        total = Cn * N
+        tw, th = -(-width // TILE_SIZE), -(-height // TILE_SIZE)
+        DC = (0 if col is None else col.shape[-1]) + _open_channels(cs)
+        packed = Cn * N > 0 and 1 <= DC + int(with_depth) <= RECORD_CHANNELS and _bin3_ok(Cn, tw, th, 0)
+        if dp is not None and not (packed and Cn == 1 and DC >= 3 and bg is None and (DC == 3 or dp.rows_hook is not None)):
+            raise NotImplementedError("data-parallel rasterization: one camera, the SH output in the first 3 colour channels (further "
+                                      "channels need SparseGradExchange.rows_hook to fold their gradient into the wire rows), no "
+                                      "backgrounds")
+        if cs is not None and not (packed and Cn == 1 and (dp is None or cs.exchange) and bg is None):
+            raise NotImplementedError("rasterization(color_source=...): one camera, at most 8 blended channels, no backgrounds")
+        # ---- allocate the outputs
+        dev, ed = means.device, bool(expected_depth)
         radii = torch.empty((Cn, N), dtype=torch.int32, device=dev)
         means2d = torch.empty((Cn, N, 2), dtype=torch.float32, device=dev)
         depths = torch.empty((Cn, N), dtype=torch.float32, device=dev)
@@ -999,193 +1244,24 @@ class _FusedRasterization(torch.autograd.Function):
         comps = torch.empty((Cn, N), dtype=torch.float32, device=dev) if calc_compensations else None
         opac_eff = torch.empty((Cn, N), dtype=torch.float32, device=dev)
         tiles_per_gauss = torch.empty((Cn, N), dtype=torch.int32, device=dev)
-        render = torch.empty((Cn, height, width, DT), dtype=torch.float32, device=dev)
+        render = torch.empty((Cn, height, width, DC + int(with_depth)), dtype=torch.float32, device=dev)
         alphas = torch.empty((Cn, height, width, 1), dtype=torch.float32, device=dev)
         last_ids = torch.empty((Cn, height, width), dtype=torch.int32, device=dev)
-        packed = total > 0 and 1 <= DT <= RECORD_CHANNELS and _bin3_ok(Cn, tw, th, 0)
-        if dp is not None and not (packed and Cn == 1 and DC >= 3 and bg is None and (DC == 3 or dp.rows_hook is not None)):
-            raise NotImplementedError("data-parallel rasterization: one camera, the SH output in the first 3 colour channels (further "
-                                      "channels need SparseGradExchange.rows_hook to fold their gradient into the wire rows), no "
-                                      "backgrounds")
-        if cs is not None and not (packed and Cn == 1 and (dp is None or getattr(cs, "exchange", False)) and bg is None):
-            raise NotImplementedError("rasterization(color_source=...): one camera, at most 8 blended channels, no backgrounds")
-        if not packed:
-            # ---- gather-based kernels (csrc/project.hip, bin.hip, blend.hip with dense attribute arrays)
-            call("mtgs_project_fwd", Cn, N, ptr(means), ptr(quats), ptr(scales), ptr(viewmats), ptr(Ks),
-                 width, height, eps2d, near_plane, far_plane, radius_clip, ptr(opacities), ptr(radii),
-                 ptr(means2d), ptr(depths), ptr(conics), ptr(comps), ptr(opac_eff), tile_size, tw, th,
-                 ptr(tiles_per_gauss), st)     # (+ the count pass of isect_tiles)
-            scan_ws, scan_bytes = _ws("mtgs_scan_workspace_bytes", total, dev)
-            _, isect_ids, flatten_ids, offsets, order, vis_ids, vis_rank = _bin_depth_ordered(
-                means2d, radii, depths, tiles_per_gauss, scan_ws, scan_bytes, tile_size, tw, th, want_rank=True)
-            dep = depths if with_depth else None
-            call("mtgs_blend_fwd", Cn, N, DC, ptr(means2d), ptr(conics), ptr(col), ptr(opac_eff), ptr(bg), ptr(dep), int(ed),
-                 width, height, tile_size, tw, th, ptr(offsets), ptr(flatten_ids), flatten_ids.numel(), ptr(render),
-                 ptr(alphas), ptr(last_ids), ptr(order), st)
-            recs = rank_ids = None
-        else:
-            # ---- packed records
-            key = (Cn, N, width, height)
-            front_ws, front_bytes = _ws("mtgs_front_workspace_bytes", total, dev)
-            # (graph mode: {packed, n_vis, M, overflow} -- words 1..3 are written by the binning, MTGS_BIN3_STATUS)
-            totals = torch.empty(4 if _graph.caps is not None else 1, dtype=torch.int64, device=dev)
-            vis_rank = torch.empty(total, dtype=torch.int32, device=dev)
-            offsets_buf = torch.empty(Cn * th * tw + 1, dtype=torch.int32, device=dev)
-            order = torch.empty(Cn * th * tw, dtype=torch.int32, device=dev)
-
-            graph_caps = _graph.caps
-            if graph_caps is not None and _graph.owner != threading.get_ident():
-                raise RuntimeError("rasterization(): mtgs_amd.graph_mode is active on another thread (fixed capacities, no host "
-                                   "read-back); serialise the two callers or leave graph_mode first")
-
-            # TOUCH FIRST (ColorSource.touch_first, opt-in): the binning needs the records' geometry only, so it runs in front of the
-            # colours, and one pass of the compositing DECISIONS (mtgs_blend_touch_packed) flags the Gaussians the frame composites
-            # from -- a few percent of the visible ones in an opaque scene.  Peek, SH evaluation and normals work on those alone.
-            touch_first = cs is not None and bool(cs.touch_first)
-            wild = cs is not None and getattr(cs, "wild", False)
-            # tile lists of this frame (thread-local mode, read once): gsplat's by default; mtgs_bin3_build flags: 1 = tight lists,
-            # 2 = sentinel-fill the tail [n_listed, M) of flatten_ids / isect_ids (tight lists, tensors sliced to gsplat's M),
-            # 4 = sentinel-fill up to the capacity (graph mode: the tensors are capacity-sized in both list modes), 16 = the frame's
-            # counts and its overflow flag as device words behind `totals` (graph mode)
-            tight = lists_are_tight()
-            list_flags = (1 if tight else 0) | (4 | 16 if graph_caps is not None else (2 if tight else 0))
-
-            def colours(b, flags):   # colours of the visible Gaussians, straight into their records
-                cap_vis = b["cap_vis"]
-                if wild:             # WildGaussians appearance colours (appearance.WildColorSource, csrc/wild.hip)
-                    cs.colour_rows(b["vis_ids"], totals, cap_vis, b["recs"], flags, st)
-                else:
-                    coef = cs.prepare(vis_rank, cap_vis, b["vis_ids"], totals, row_flags=flags)    # (row-lazy optimizer: up-to-date coefficient rows, compact)
-                    call("mtgs_vis_color_fwd_dirs", cs.n_nodes, ptr(cs.table), cs.degree, ptr(cs.cam), ptr(means), ptr(b["vis_ids"]),
-                         ptr(totals), cap_vis, ptr(b["recs"]), ptr(b["vis_mask"]), ptr(coef), 0 if coef is None else coef.stride(0),
-                         ptr(flags), ptr(cs.dirs), st)
-                if n2c is not None:  # ... and their camera-space normals (channels 3..5)
-                    call("mtgs_normals_fwd_rows", cap_vis, ptr(b["vis_ids"]), ptr(totals), ptr(quats), ptr(scales), ptr(means),
-                         ptr(n2c), ptr(b["recs"]), 3, ptr(flags), st)
-
-            def bin_ws(cap_vis, cap_M):      # the binning's workspace, 256-byte aligned: (tensor, pointer, bytes, bytes of its control words)
-                nbytes, cbytes = C.c_size_t(0), C.c_size_t(0)
-                call("mtgs_bin3_workspace_bytes", Cn, tw, th, cap_vis, cap_M, C.byref(nbytes))
-                call("mtgs_bin3_control_bytes", Cn, tw, th, C.byref(cbytes))
-                ws = torch.empty(nbytes.value + 256, dtype=torch.uint8, device=dev)
-                return ws, ws.data_ptr() + (-ws.data_ptr()) % 256, nbytes.value, cbytes.value
-
-            def front(cap_vis, repeat=False, prezero=None):
-                # prezero = bin_ws(...) of the binning that follows: its control words are cleared by the compaction kernel here
-                # repeat=True: the capacity-overflow repeat of a frame.  The visibility map / row count of the exchange do not
-                # depend on cap_vis and are already on their way: they are neither rewritten nor gathered a second time
-                # (a second meta all-gather on ONE rank would desynchronise the ranks' collectives).
-                dpf = dp if not repeat else None
-                b = {"recs": torch.empty((cap_vis, 16), dtype=torch.float32, device=dev),
-                     "vis_ids": torch.empty(cap_vis, dtype=torch.int32, device=dev),
-                     "vis_keys": torch.empty(cap_vis, dtype=torch.int64, device=dev), "cap_vis": cap_vis,
-                     "vis_mask": torch.empty(cap_vis, dtype=torch.uint8, device=dev) if cs is not None else None}
-                mailbox, tag = _host_mailbox() if graph_caps is None else (None, 0)
-                call("mtgs_front_fwd", Cn, N, ptr(means), ptr(quats), ptr(scales), ptr(viewmats), ptr(Ks), width, height,
-                     eps2d, near_plane, far_plane, radius_clip, ptr(opacities), ptr(col), DC, int(with_depth), ptr(radii),
-                     ptr(means2d), ptr(depths), ptr(conics), ptr(comps), ptr(opac_eff), tile_size, tw, th,
-                     ptr(tiles_per_gauss), ptr(b["recs"]), ptr(b["vis_ids"]), ptr(b["vis_keys"]),
-                     ptr(vis_rank), cap_vis, *(dpf.front_pointers() if dpf is not None else (None, None, None)),
-                     (1 if dp is not None else 0) if cs is None else (3 if c_open == 6 else 2), ptr(totals),
-                     None if mailbox is None else mailbox.data_ptr(), tag,
-                     None if prezero is None else prezero[1], 0 if prezero is None else prezero[3],
-                     ptr(front_ws), front_bytes, st)
-                if cs is not None and not touch_first:
-                    colours(b, None)
-                b["mailbox"], b["tag"] = mailbox, tag
-                if dpf is not None:
-                    dpf.after_front()      # the visibility maps travel while this frame is composited
-                return b
-
-            ctx_box = {}
-
-            def rest(b, cap_M, prezeroed=None):
-                cap_alloc = max(cap_M, 1)
-                out = {"rank_ids": torch.empty(cap_alloc, dtype=torch.int32, device=dev),
-                       "flatten_ids": torch.empty(cap_alloc, dtype=torch.int32, device=dev),
-                       "isect_ids": torch.empty(cap_alloc, dtype=torch.int64, device=dev)}
-                ws, ws_ptr, ws_bytes, _ = prezeroed if prezeroed is not None else bin_ws(b["cap_vis"], cap_M)
-                call("mtgs_bin3_build", Cn, N, tile_size, tw, th, ptr(totals), b["cap_vis"], cap_M, ptr(b["recs"]),
-                     ptr(b["vis_ids"]), ptr(b["vis_keys"]), ptr(out["rank_ids"]),
-                     ptr(out["flatten_ids"]), ptr(out["isect_ids"]), ptr(offsets_buf), ptr(order),
-                     list_flags | (8 if prezeroed is not None else 0), ws_ptr, ws_bytes, st)
-                if touch_first:
-                    flags = torch.empty(max(b["cap_vis"], 1), dtype=torch.uint8, device=dev)
-                    call("mtgs_blend_touch_packed", Cn, ptr(b["recs"]), width, height, tw, th, ptr(offsets_buf), ptr(out["rank_ids"]),
-                         ptr(order), ptr(flags), b["cap_vis"], st)
-                    colours(b, flags)
-                # a training forward: its compositing kernel (VALU-bound, HBM mostly idle) clears what the backward pass will want
-                # zeroed -- the gradient rows of the compositing backward, the dL/dcoeffs of the SH backwards (_Prefill)
-                z_ptr, z_bytes = None, 0
-                if _prefill.enabled and _prefill.in_forward and any(ctx.needs_input_grad) and dp is None and ctx_box.get("rows") is None:
-                    RS_ = -(-(8 + DC + int(with_depth)) // 16) * 16
-                    n_rows_ = max(b["cap_vis"], 1) * RS_
-                    # (gsplat's sh_degree call style: the dense [N, 16, 3] coefficient gradient too -- the backward then writes the
-                    #  rows of the Gaussians with a cotangent straight into it, mtgs_vis_color_bwd(dense_rows))
-                    n_coef_ = N * 48 if (cs is not None and cs.autograd and cs.width == 48 and (cs.n_nodes == 1 or cs.dirs is not None)
-                                         and (graph_caps is None or cs.dirs is not None)
-                                         and (ctx.needs_input_grad[20] or any(ctx.needs_input_grad[22:22 + cs.n_nodes - 1]))) else 0
-                    z_ptr, z_bytes, own_ = _prefill.take(dev, n_rows_ + n_coef_, only=getattr(_sh_scope, "reqs", ()))
-                    ctx_box["rows"] = own_[:n_rows_].view(max(b["cap_vis"], 1), RS_)
-                    if n_coef_:
-                        ctx_box["coeffs"] = own_[n_rows_:].view(N, 16, 3)
-                elif dp is not None and getattr(dp, "zero_region", None) is not None and any(ctx.needs_input_grad):
-                    # data-parallel frame: the dense sums the exchange will return (SparseGradExchange.prezero) are cleared here too
-                    z_ptr, z_bytes = dp.zero_region
-                call("mtgs_blend_fwd_packed", Cn, DC, int(with_depth), ptr(b["recs"]), ptr(bg), int(ed), width, height, tw, th,
-                     ptr(offsets_buf), ptr(out["rank_ids"]), ptr(render), ptr(alphas), ptr(last_ids), ptr(order), z_ptr, z_bytes, st)
-                return out
-
-            caps = _force_caps or (_size_plan.caps(key, total) if speculative_sizing else None)
-            if caps is not None and not _bin3_ok(Cn, tw, th, caps[1]):
-                caps = None
-            if graph_caps is not None:
-                # graph mode: fixed capacities, nothing waits for the host; the counts stay on the device
-                if dp is not None or not _bin3_ok(Cn, tw, th, graph_caps[1]):
-                    raise NotImplementedError("graph_mode: unsupported configuration (data-parallel exchange / capacity >= 2^30)")
-                pz = bin_ws(min(graph_caps[0], total), graph_caps[1])
-                b = front(min(graph_caps[0], total), prezero=pz)
-                out = rest(b, graph_caps[1], prezeroed=pz)
-                n_vis, M = b["cap_vis"], graph_caps[1]
-            elif caps is not None:
-                pz = bin_ws(min(caps[0], total), caps[1])
-                b = front(min(caps[0], total), prezero=pz)
-                out = rest(b, caps[1], prezeroed=pz)      # enqueued before the totals are known
-                n_vis, M = _wait_mailbox(b["mailbox"], b["tag"], totals, total)
-                if n_vis > b["cap_vis"] or M > caps[1]:   # capacities too small: repeat with exact sizes
-                    if not _bin3_ok(Cn, tw, th, M):
-                        raise NotImplementedError(f"rasterization: {M} tile intersections in one call (limit 2^30)")
-                    if n_vis > b["cap_vis"]:
-                        b = front(n_vis, repeat=True)
-                    out = rest(b, M)
-            else:
-                b = front(total)
-                n_vis, M = _wait_mailbox(b["mailbox"], b["tag"], totals, total)
-                if not _bin3_ok(Cn, tw, th, M):
-                    raise NotImplementedError(f"rasterization: {M} tile intersections in one call (limit 2^30)")
-                b["cap_vis"] = max(n_vis, 0)              # (buffers are larger; the kernels only need a bound)
-                out = rest(b, M)
-            if graph_caps is None:
-                _size_plan.update(key, n_vis, M)
-            recs, vis_ids = b["recs"], b["vis_ids"][:n_vis]
-            rank_ids, flatten_ids, isect_ids = out["rank_ids"][:M], out["flatten_ids"][:M], out["isect_ids"][:M]
-            offsets = offsets_buf[:Cn * th * tw].view(Cn, th, tw)
-            offsets._mtgs_tile_order = order
-            if tight or graph_caps is not None:
-                offsets._mtgs_n_listed = offsets_buf[Cn * th * tw]     # (device scalar: the number of pairs in the lists)
-            isect_ids._mtgs_offsets = offsets
-        if not packed:
-            totals = torch.zeros(1, dtype=torch.int64, device=dev)
-        ctx.save_for_backward(means, quats, scales, opacities, col, viewmats, Ks, bg, radii, means2d, depths, conics,
-                              comps, opac_eff, offsets if not packed else offsets_buf, flatten_ids, alphas, last_ids, order,
-                              vis_ids, vis_rank, render if ed else None, recs, rank_ids, totals)
-        ctx.cs, ctx.vis_mask, ctx.cap_vis = cs, (b["vis_mask"] if cs is not None else None), (b["cap_vis"] if packed else 0)
-        ctx.zero_rows = ctx_box.get("rows") if packed else None      # gradient rows the forward's compositing kernel cleared
+        dims = (Cn, N, width, height, tw, th, DC, int(with_depth), ed, eps2d, near_plane, far_plane, radius_clip)
+        outs = (radii, means2d, depths, conics, comps, opac_eff, tiles_per_gauss, render, alphas, last_ids)
+        # ---- run the packed path or the gather path
+        (isect_ids, flatten_ids, offsets, offsets_saved, order, vis_ids, vis_rank, totals, recs, rank_ids, ctx.vis_mask, ctx.cap_vis,
+         ctx.zero_rows, ctx.zero_coeffs) = (_packed_path(ins, dims, outs, ctx.needs_input_grad, dp, cs) if packed
+                                             else _gather_path(ins, dims, outs))
+        # ---- save
+        ctx.save_for_backward(*ins, radii, means2d, depths, conics, comps, opac_eff, offsets_saved, flatten_ids, alphas, last_ids,
+                              order, vis_ids, vis_rank, render if ed else None, recs, rank_ids, totals)
+        ctx.cs = cs
         ctx.sh_reqs = [weakref.ref(r) for r in getattr(_sh_scope, "reqs", ())]      # (what the forward did not serve, the backward may)
-        ctx.zero_coeffs = ctx_box.get("coeffs") if packed else None
-        ctx.n2c = n2c
+        ctx.means2d_ref = None           # fused_rasterization: a weak reference to the means2d it hands out
+        ctx.n2c = None if cs is None else cs.camera_normals
         ctx.graph = packed and _graph.caps is not None
-        ctx.dims = (width, height, tile_size, tw, th, DC, bool(with_depth), ed, float(eps2d))
+        ctx.dims = (width, height, TILE_SIZE, tw, th, DC, bool(with_depth), ed, float(eps2d))
         ctx.absgrad = bool(absgrad)
         ctx.packed = packed
         ctx.dp = dp
@@ -1207,10 +1283,23 @@ class _FusedRasterization(torch.autograd.Function):
         n_vis = vis_ids.numel()
         DT = DC + int(with_depth)
         dep = depths if with_depth else None
+        cs, need = ctx.cs, ctx.needs_input_grad
+        # gradients that reached the projection outputs directly (losses on info["means2d"] / ["depths"] / ...)
+        direct = [g for g in (g_means2d, g_conics, g_opac, g_depths, g_comps) if g is not None]
+        m2d_out = ctx.means2d_ref() if ctx.means2d_ref is not None else None
+        # the packed compositing backward runs; it leaves RAW MOMENT rows (blend.hip / include/mtgs_rast.h): their consumer -- the
+        # projection backward, per visible Gaussian -- converts them in place to {v_xy, |v_xy|, v_conic, v_opacity_eff}
+        raw = bool(ctx.packed and rank_ids.numel() > 0 and (v_render is not None or v_alphas is not None))
+        plan = _backward_plan(packed=raw, Cn=Cn, N=N, n_vis=n_vis, DC=DC, absgrad=ctx.absgrad, has_dp=ctx.dp is not None,
+                              info_grads=bool(direct), m2d_alive=m2d_out is not None,
+                              m2d_retains=m2d_out is not None and m2d_out.retains_grad, need_colors=need[_IN["colors"]],
+                              open_channels=_open_channels(cs), geometry_rows=cs is not None and cs.geometry_rows,
+                              want_grad_rows=cs is not None and cs.want_grad_rows, prefill_enabled=_prefill.enabled,
+                              zeroed_outputs=_zeroed_outputs)
         # compact gradient rows, one per VISIBLE (camera, Gaussian) pair:
         #   [xy 2 | |xy| 2 | conic 3 | opacity 1 | colour DC | depth 1 | pad]
-        RS = -(-(8 + DT) // 16) * 16
-        G = getattr(ctx, "zero_rows", None)
+        RS = _row_stride(DT)
+        G = ctx.zero_rows
         if G is not None and G.shape[1] == RS and G.shape[0] >= max(n_vis, 1):
             ctx.zero_rows = None            # (cleared by the forward's compositing kernel; a second backward of the node takes the else)
             G = G[:max(n_vis, 1)]
@@ -1219,7 +1308,7 @@ class _FusedRasterization(torch.autograd.Function):
         r_xy, r_abs, r_con, r_opa = G[:, 0:2], G[:, 2:4], G[:, 4:7], G[:, 7]
         r_col = G[:, 8:8 + DC] if DC else None
         r_dep = G[:, 8 + DC] if with_depth else None
-        zeroed_out = None
+        Z = None      # plan.zeroed: the dense gradients by name, views of the region the compositing backward clears
         if v_render is not None or v_alphas is not None:
             if v_render is None:
                 v_render = torch.zeros((Cn, height, width, DT), dtype=torch.float32, device=dev)
@@ -1233,11 +1322,9 @@ class _FusedRasterization(torch.autograd.Function):
                     # extra colour channels: zeros for the ~94 % of the Gaussians without a gradient): the compositing backward is
                     # VALU-bound and clears them beside its own work, the projection backward then writes the rows that have a gradient
                     # to their places and its streaming pass over all N does not run (mtgs_project_bwd_zeroed)
-                    zplan = _zeroed_outputs_plan(ctx, Cn, N, n_vis, DC, g_means2d, g_depths, g_conics, g_comps, g_opac)
-                    z_ptr, z_bytes, z_own = _prefill.take(dev, 0 if zplan is None else zplan["floats"],
-                                                          only=[r for r in (w() for w in getattr(ctx, "sh_reqs", ())) if r is not None])
-                    if zplan is not None:
-                        zeroed_out = {k: z_own[o:o + n_].view(shape) for k, (o, n_, shape) in zplan["views"].items()}
+                    z_ptr, z_bytes, z_own = _prefill.take(dev, plan.floats, only=[r for r in (w() for w in ctx.sh_reqs) if r is not None])
+                    if plan.zeroed:
+                        Z = {k: z_own[o:o + n_].view(shape) for k, (o, n_, shape) in plan.views.items()}
                     call("mtgs_blend_bwd_packed", Cn, DC, int(with_depth), ptr(recs), ptr(bg), int(ed), width, height, tw, th,
                          ptr(offsets), ptr(rank_ids), ptr(alphas), ptr(last_ids), ptr(render), ptr(v_render), ptr(v_alphas),
                          ptr(G), RS, int(ctx.absgrad), ptr(order), z_ptr, z_bytes, st)
@@ -1247,24 +1334,20 @@ class _FusedRasterization(torch.autograd.Function):
                      ptr(last_ids), ptr(render), ptr(v_render), ptr(v_alphas), ptr(r_xy),
                      ptr(r_abs) if ctx.absgrad else None, ptr(r_con), ptr(r_col), ptr(r_dep), ptr(r_opa),
                      host_i64([RS] * 6), ptr(vis_rank), ptr(order), st)
-        # the packed compositing backward leaves RAW MOMENT rows (blend.hip / include/mtgs_rast.h): their consumer -- the
-        # projection backward, per visible Gaussian -- converts them in place to {v_xy, |v_xy|, v_conic, v_opacity_eff}
-        raw = bool(ctx.packed and rank_ids.numel() > 0 and (v_render is not None or v_alphas is not None))
         if _debug_rows is not None:
             _debug_rows.update(G=G, vis_ids=vis_ids, DC=DC, with_depth=with_depth)
-        cs = ctx.cs
         wild_grads = None
-        if cs is not None and getattr(cs, "wild", False):
-            # WildGaussians appearance colours: dense gradients of the source's inputs (22 ..) from the colour columns of the rows
-            wild_grads = cs.backward_rows(ctx.needs_input_grad[22:], vis_ids, totals, n_vis, G, RS, st)
-        elif cs is not None and not getattr(cs, "exchange", False):      # (data-parallel frames: the colour gradient travels as v_rgb in the wire rows)
+        if cs is not None and cs.wild:
+            # WildGaussians appearance colours: dense gradients of the source's inputs from the colour columns of the rows
+            wild_grads = cs.backward_rows(need[_tail_inputs(cs)[1]:], vis_ids, totals, n_vis, G, RS, st)
+        elif cs is not None and not cs.exchange:      # (data-parallel frames: the colour gradient travels as v_rgb in the wire rows)
             # visibility-first colours: d L / d (SH coefficients) of the VISIBLE Gaussians as 192-byte rows; the optimizer takes
             # them through the row map (vis_rank: rank or -1) -- no dense [N, (T,) K, 3] gradient is written
-            dense_coeffs = getattr(ctx, "zero_coeffs", None) if cs.autograd else None      # (zeroed by the forward's compositing kernel)
+            dense_coeffs = ctx.zero_coeffs if cs.autograd else None      # (zeroed by the forward's compositing kernel)
             ctx.zero_coeffs = None
-            n_c = 22 + cs.n_nodes - 1      # (inputs 20, 22 .. n_c - 1: the nodes' coefficient tensors; n_c ..: their direction tensors, if given)
-            need_coef = bool(ctx.needs_input_grad[20] or any(ctx.needs_input_grad[22:n_c]))
-            need_dirs = bool(getattr(cs, "dirs_inputs", None)) and any(ctx.needs_input_grad[n_c:])
+            c_at, d_at = _tail_inputs(cs)
+            need_coef = _needs_coeffs(need, cs)
+            need_dirs = bool(cs.dirs_inputs) and any(need[d_at:])
             want_dirs = cs.autograd and (cs.dirs is None or need_dirs)      # (given directions carry a gradient only with a camera optimizer)
             feat = dir_rows = dir_part = None
             if not (cs.autograd and cs.dirs is not None and not (need_coef or need_dirs)):      # (frozen coefficients: nothing to do)
@@ -1278,9 +1361,9 @@ class _FusedRasterization(torch.autograd.Function):
         if ctx.dp is not None:
             # data-parallel mode: the per-visible VJP writes this rank's wire rows (index order) into the exchange's send
             # buffer; dense gradients are rebuilt for all ranks at once by SparseGradExchange.finish()
-            if any(g is not None for g in (g_means2d, g_depths, g_conics, g_comps, g_opac)):
+            if direct:
                 raise NotImplementedError("data-parallel rasterization: gradients on info[...] tensors")
-            v_viewmats = torch.empty_like(viewmats) if ctx.needs_input_grad[5] else None
+            v_viewmats = torch.empty_like(viewmats) if need[_IN["viewmats"]] else None
             call("mtgs_project_bwd_rows", N, ptr(means), ptr(quats), ptr(scales), ptr(viewmats), ptr(Ks), width, height, eps2d,
                  ptr(conics), ptr(comps), ptr(opacities), ptr(G), RS, DC, int(with_depth),
                  *((ptr(col), 1) if cs is None else (ptr(ctx.vis_mask), 2)),      # (the clamp's pass-through rule: from x, or from the colour kernel's bits)
@@ -1288,10 +1371,8 @@ class _FusedRasterization(torch.autograd.Function):
             if ctx.dp.rows_hook is not None:    # camera-dependent extra channels (normals): their VJP goes into the rows here
                 ctx.dp.rows_hook(G, RS, vis_ids, n_vis)
             ctx.dp.after_backward(n_vis, G, vis_ids)
-            return (None, None, None, None, None, v_viewmats, None, None) + (None,) * (len(ctx.needs_input_grad) - 8)
-        # gradients that reached the projection outputs directly (losses on info["means2d"] / ["depths"] / ...):
-        # added to the visible rows (culled pairs have no gradient path in gsplat either)
-        direct = [g for g in (g_means2d, g_conics, g_opac, g_depths, g_comps) if g is not None]
+            return _input_grads(ctx, viewmats=v_viewmats)
+        # the direct gradients are added to the visible rows (culled pairs have no gradient path in gsplat either)
         if direct and ctx.graph:
             raise NotImplementedError("graph_mode: gradients on info[...] tensors (the visible list is capacity-sized)")
         if raw and n_vis > 0 and (direct or Cn != 1):
@@ -1321,35 +1402,30 @@ class _FusedRasterization(torch.autograd.Function):
         r_cmp = None
         if comps is not None and g_comps is not None and n_vis > 0:
             r_cmp = g_comps.reshape(Cn * N)[vi].contiguous()
-        need = ctx.needs_input_grad
-        geo_rows = bool(cs is not None and getattr(cs, "geometry_rows", False) and not direct and n_vis > 0)
+        geo_rows, c0 = plan.geo_rows, plan.c0
         if geo_rows and (any(g[4] for g in cs.node_geometry) or cs.autograd):
             raise NotImplementedError("ColorSource.geometry_rows: static nodes only (a rigid node's pose gradient is a sum over its Gaussians)")
-        if zeroed_out is not None and (geo_rows or direct or not raw):
-            zeroed_out = None      # (cannot happen: _zeroed_outputs_plan tests the same conditions)
-        Z = zeroed_out or {}
-        v_means = None if geo_rows else Z.get("means", None) if Z else torch.empty_like(means)
-        v_quats = None if geo_rows else Z.get("quats", None) if Z else torch.empty_like(quats)
-        v_scales = None if geo_rows else Z.get("scales", None) if Z else torch.empty_like(scales)
-        v_opacities = None if geo_rows else Z.get("opacities", None) if Z else torch.empty_like(opacities)
-        v_viewmats = torch.empty_like(viewmats) if need[5] else None
-        m2d_out = ctx.means2d_ref() if getattr(ctx, "means2d_ref", None) is not None else None
-        want_m2d = m2d_out is not None and m2d_out.retains_grad
-        rows_only = cs is not None and getattr(cs, "want_grad_rows", False)
-        if geo_rows and not rows_only:
+
+        def dense(name, shape):      # a dense gradient this node returns: its view of the cleared region, or memory the streaming pass fills
+            return Z[name] if Z is not None else torch.empty(shape, dtype=torch.float32, device=dev)
+        v_means = None if geo_rows else dense("means", means.shape)
+        v_quats = None if geo_rows else dense("quats", quats.shape)
+        v_scales = None if geo_rows else dense("scales", scales.shape)
+        v_opacities = None if geo_rows else dense("opacities", opacities.shape)
+        v_viewmats = torch.empty_like(viewmats) if need[_IN["viewmats"]] else None
+        if geo_rows and not plan.rows_only:
             raise NotImplementedError("ColorSource.geometry_rows needs want_grad_rows (no dense by-products of the projection backward)")
-        if rows_only:   # the caller takes the 2-D gradients from the compact rows (densify.update_statistics_rows): no dense absgrad
+        if plan.rows_only:   # the caller takes the 2-D gradients from the compact rows (densify.update_statistics_rows): no dense absgrad
             cs.grad_rows, cs.grad_row_ids, cs.grad_row_count = G, vis_ids, (totals if ctx.graph else None)
-        d_m2d = (Z["m2d"] if Z else torch.empty((Cn, N, 2), dtype=torch.float32, device=dev)) if want_m2d else None
-        d_abs = (Z["abs"] if Z else torch.empty((Cn, N, 2), dtype=torch.float32, device=dev)) if (ctx.absgrad and m2d_out is not None and not rows_only) else None
-        c0 = 0 if cs is None else (6 if ctx.n2c is not None else 3)   # (the dense colour gradient covers the other channels only)
+        d_m2d = dense("m2d", (Cn, N, 2)) if plan.want_m2d else None
+        d_abs = dense("abs", (Cn, N, 2)) if plan.want_abs else None
         q_rows = None
         if cs is not None and ctx.n2c is not None:   # the normals' gradient: quaternion rows of the visible Gaussians
             q_rows = torch.empty((max(n_vis, 1), 4), dtype=torch.float32, device=dev)
             call("mtgs_normals_bwd_qrows", n_vis, ptr(vis_ids), ptr(totals) if ctx.graph else None, ptr(quats), ptr(scales), ptr(means),
                  ptr(ctx.n2c), ptr(G), RS, 8 + 3, ptr(q_rows), st)
-        d_col = (Z["col"] if Z else torch.empty((Cn, N, DC - c0), dtype=torch.float32, device=dev)) if (DC - c0 and need[4]) else None
-        if geo_rows and (d_col is not None or want_m2d):
+        d_col = dense("col", (Cn, N, DC - c0)) if plan.want_col else None      # (the dense colour gradient covers the caller's channels only)
+        if geo_rows and (d_col is not None or plan.want_m2d):
             raise NotImplementedError("ColorSource.geometry_rows: no extra colour channels with a gradient, no retain_grad() on means2d")
         vis_ws = torch.empty((max(n_vis, 1), 12), dtype=torch.float32, device=dev)  # scratch of the compact VJP
         vm_part = None      # ... and of the camera gradient: the workgroups' partial sums (added up in a fixed order, no atomics)
@@ -1357,7 +1433,7 @@ class _FusedRasterization(torch.autograd.Function):
             nb = C.c_int64(0)
             call("mtgs_project_bwd_blocks", n_vis, C.byref(nb))
             vm_part = torch.empty(nb.value * 12, dtype=torch.float32, device=dev)
-        call("mtgs_project_bwd_zeroed" if Z else "mtgs_project_bwd", Cn, N, ptr(means), ptr(quats), ptr(scales), ptr(viewmats), ptr(Ks), width, height,
+        call("mtgs_project_bwd_zeroed" if Z is not None else "mtgs_project_bwd", Cn, N, ptr(means), ptr(quats), ptr(scales), ptr(viewmats), ptr(Ks), width, height,
              eps2d, ptr(radii), ptr(conics), ptr(comps), ptr(opacities), ptr(r_xy), ptr(r_dep_total), ptr(r_con),
              ptr(r_cmp), ptr(r_opa), ptr(v_means), ptr(v_quats), ptr(v_scales), ptr(v_viewmats), ptr(v_opacities),
              host_i64([RS, r_dep_total.stride(0), RS, 1, RS]), ptr(vis_rank), ptr(r_abs),
@@ -1367,7 +1443,7 @@ class _FusedRasterization(torch.autograd.Function):
              ptr(dir_rows) if (cs is not None and cs.autograd and cs.dirs is None and n_vis > 0) else None,      # (differentiable view directions: dirs = means - camera position)
              ptr(G) if raw else None, ptr(recs) if (raw and Cn == 1) else None, ptr(vm_part), st)
         d_coeffs = d_campos = None
-        d_more = (None,) * max(len(ctx.needs_input_grad) - 22, 0) if wild_grads is None else wild_grads
+        d_tail = () if wild_grads is None else wild_grads
         if cs is not None and cs.autograd:
             if ctx.graph and cs.dirs is None:
                 raise NotImplementedError("graph_mode: rasterization(sh_degree=...) (dense coefficient gradient)")
@@ -1378,70 +1454,66 @@ class _FusedRasterization(torch.autograd.Function):
                 d_coeffs = torch.empty((N, K3 // 3, 3), dtype=torch.float32, device=dev)
                 call("mtgs_rows_expand", N, K3, ptr(vis_rank), ptr(feat), 48, ptr(d_coeffs), st)
             if cs.dirs is not None:
-                d_campos = None
-                n_c = 22 + cs.n_nodes - 1
-                need_c = [ctx.needs_input_grad[20]] + list(ctx.needs_input_grad[22:n_c])
+                need_c = [need[_IN["sh_coeffs"]]] + list(need[c_at:d_at])
                 d_dirs = ()
-                if len(ctx.needs_input_grad) > n_c:      # directions with a gradient: the visible rows scattered into a dense [N, 3]
+                if len(need) > d_at:      # directions with a gradient: the visible rows scattered into a dense [N, 3]
                     v_dirs = torch.zeros((N, 3), dtype=torch.float32, device=dev)
                     if dir_rows is not None and n_vis > 0:
                         v_dirs.index_copy_(0, vis_ids[:n_vis].long(), dir_rows[:n_vis])
-                    d_dirs = tuple(v_dirs[s:s + n_] if nd else None for (s, n_, *_), nd in zip(cs.node_params, ctx.needs_input_grad[n_c:]))
+                    d_dirs = tuple(v_dirs[s:s + n_] if nd else None for (s, n_, *_), nd in zip(cs.node_params, need[d_at:]))
                 if d_coeffs is not None and not any(need_c):
                     d_coeffs = None
+                d_tail = (None,) * (cs.n_nodes - 1)
                 if cs.n_nodes > 1 and d_coeffs is not None:      # one dense buffer in collected order: every node's gradient is its slice
                     parts = [d_coeffs[s:s + n_] if nd else None for (s, n_, *_), nd in zip(cs.node_params, need_c)]
-                    d_coeffs, d_more = parts[0], tuple(parts[1:])
-                else:
-                    d_more = (None,) * (cs.n_nodes - 1)
-                d_more = d_more + d_dirs
+                    d_coeffs, d_tail = parts[0], tuple(parts[1:])
+                d_tail = d_tail + d_dirs
             elif n_vis > 0:
                 d_campos = -dir_part.sum(0)
             else:
                 d_campos = torch.zeros(3, dtype=torch.float32, device=dev)
-        if want_m2d:
+        if plan.want_m2d:
             m2d_out.grad = d_m2d      # what retain_grad() would have kept: the gradient reaching means2d
         if d_abs is not None:
             m2d_out.absgrad = d_abs   # gsplat: set in rasterize_to_pixels' backward (mtgs_scene_graph.py:1172)
         v_bg = None
-        if bg is not None and need[7] and v_render is not None:
+        if bg is not None and need[_IN["backgrounds"]] and v_render is not None:
             v_bg = (v_render[..., :DC] * (1.0 - alphas)).sum(dim=(1, 2))
         if geo_rows:      # the per-visible rows ARE the geometry gradient (ColorSource.apply_to -> mtgs_node_bwd_rows -> the optimizer)
             cs.geo_ws = (vis_ws, vis_ids, totals if ctx.graph else None)
-            return (None, None, None, None, d_col, v_viewmats, None, v_bg) + (None,) * 12 + (d_coeffs, d_campos) + d_more
-        return (v_means if need[0] else None, v_quats if need[1] else None, v_scales if need[2] else None,
-                v_opacities if need[3] else None, d_col, v_viewmats, None, v_bg) + (None,) * 12 + (d_coeffs, d_campos) + d_more
+        return _input_grads(ctx, d_tail, means=v_means if need[_IN["means"]] else None, quats=v_quats if need[_IN["quats"]] else None,
+                            scales=v_scales if need[_IN["scales"]] else None,
+                            opacities=v_opacities if need[_IN["opacities"]] else None, colors=d_col, viewmats=v_viewmats,
+                            backgrounds=v_bg, sh_coeffs=d_coeffs, campos=d_campos)
 
 
-def _zeroed_outputs_plan(ctx, Cn, N, n_vis, DC, g_means2d, g_depths, g_conics, g_comps, g_opac):
-    """Layout of the dense gradients of a _FusedRasterization backward inside ONE region that its compositing backward clears
-    (see the call site), or None when this backward does not take that form: {"floats": total, "views": {name: (offset, count, shape)}},
-    every view 16-byte aligned.  Mirrors the decisions the backward takes further down (which by-products it returns)."""
-    if not (_prefill.enabled and _zeroed_outputs and ctx.packed and Cn == 1 and ctx.dp is None and n_vis > 0 and N > 0):
-        return None
-    if any(g is not None for g in (g_means2d, g_depths, g_conics, g_comps, g_opac)):      # (a loss on info[...]: the generic path)
-        return None
-    cs = ctx.cs
-    if cs is not None and getattr(cs, "geometry_rows", False):
-        return None
-    m2d_out = ctx.means2d_ref() if getattr(ctx, "means2d_ref", None) is not None else None
-    want_m2d = m2d_out is not None and m2d_out.retains_grad
-    rows_only = cs is not None and getattr(cs, "want_grad_rows", False)
-    want_abs = bool(ctx.absgrad and m2d_out is not None and not rows_only)
-    c0 = 0 if cs is None else (6 if ctx.n2c is not None else 3)
-    want_col = bool(DC - c0 and ctx.needs_input_grad[4])
-    items = [("means", N * 3, (N, 3)), ("quats", N * 4, (N, 4)), ("scales", N * 3, (N, 3)), ("opacities", N, (N,))]
-    if want_m2d:
-        items.append(("m2d", N * 2, (1, N, 2)))
-    if want_abs:
-        items.append(("abs", N * 2, (1, N, 2)))
-    if want_col:
-        items.append(("col", N * (DC - c0), (1, N, DC - c0)))
-    views, at = {}, 0
-    for name, n_, shape in items:
-        views[name] = (at, n_, shape)
-        at += -(-n_ // 4) * 4
-    return {"floats": at, "views": views}
+# ---- the inputs of _FusedRasterization by name: every index into needs_input_grad and every returned gradient goes through these
+_fwd = _FusedRasterization.forward.__code__
+_INPUTS = _fwd.co_varnames[1:_fwd.co_argcount]      # forward's named inputs in its order (without ctx and *sh_more)
+_IN = {name: i for i, name in enumerate(_INPUTS)}
+
+
+def _tail_inputs(cs):
+    """Layout of forward's var-positional inputs, which follow `campos`: the coefficient tensors of the colour source's nodes 1 .. n - 1
+    (node 0's is `sh_coeffs`), then its direction tensors (cs.dirs_inputs) or its wild inputs (cs.wild_inputs: one node, no directions).
+    Returns (position of the first coefficient tensor, position of the first direction / wild tensor)."""
+    return len(_INPUTS), len(_INPUTS) + cs.n_nodes - 1
+
+
+def _needs_coeffs(need, cs) -> bool:
+    """A coefficient tensor of the colour source needs a gradient (need: the node's needs_input_grad)."""
+    c_at, d_at = _tail_inputs(cs)
+    return bool(need[_IN["sh_coeffs"]] or any(need[c_at:d_at]))
+
+
+def _input_grads(ctx, tail=(), **named):
+    """A backward's return value: the gradients of the named inputs, `tail` for the var-positional ones, None for all others."""
+    grads = [None] * len(ctx.needs_input_grad)
+    for name, g in named.items():
+        grads[_IN[name]] = g
+    if tail:
+        grads[len(_INPUTS):len(_INPUTS) + len(tail)] = tail
+    return tuple(grads)
 
 
 _zeroed_outputs = os.environ.get("MTGS_ZEROED_OUTPUTS", "1") == "1"      # (development switch: 0 = the streaming expansion pass of rounds 1-5)
@@ -1463,21 +1535,18 @@ def fused_rasterization(means, quats, scales, opacities, colors, viewmats, Ks, b
                         dp=None, color_source=None, sh_source=None):
     """One-node projection + binning + compositing (see _FusedRasterization).  colors[C,N,D] | None.
     Returns (render, alphas, dict of gsplat's meta tensors)."""
-    import weakref
     if colors is not None or color_source is not None:
-        opened = 0 if color_source is None else (6 if getattr(color_source, "camera_normals", None) is not None else 3)
-        total = (0 if colors is None else colors.shape[-1]) + opened + int(with_depth)
+        total = (0 if colors is None else colors.shape[-1]) + _open_channels(color_source) + int(with_depth)
         if total not in SUPPORTED_CHANNELS:
             raise ValueError(f"fused_rasterization: {total} blended channels (supported: {SUPPORTED_CHANNELS})")
     # the spherical_harmonics() forwards these colours come from: only THEIR backward's zeros ride on this rasterization (_Prefill)
     _sh_scope.reqs = _prefill.behind(colors) if (_prefill.enabled and colors is not None and colors.requires_grad) else ()
+    tail = () if color_source is None else (*(color_source.dirs_inputs or ()), *(color_source.wild_inputs or ()))      # (see _tail_inputs)
     try:
         out = _FusedRasterization.apply(means, quats, scales, opacities, colors, viewmats, Ks, backgrounds, int(width),
                                         int(height), float(eps2d), float(near_plane), float(far_plane), float(radius_clip),
                                         bool(calc_compensations), bool(with_depth), bool(expected_depth), bool(absgrad), dp,
-                                        color_source, *_sh_inputs(sh_source),
-                                        *(getattr(color_source, "dirs_inputs", None) or ()),
-                                        *(getattr(color_source, "wild_inputs", None) or ()))
+                                        color_source, *_sh_inputs(sh_source), *tail)
     finally:
         _sh_scope.reqs = ()
     (render, alphas, radii, means2d, depths, conics, comps, opac_eff, tiles_per_gauss, isect_ids, flatten_ids,

@@ -1,4 +1,4 @@
-"""The dense gradients of rasterization() written WITHOUT a streaming pass (mtgs_amd/wrapper.py::_zeroed_outputs_plan,
+"""The dense gradients of rasterization() written WITHOUT a streaming pass (mtgs_amd/wrapper.py::_backward_plan,
 csrc/project_bwd.hip::mtgs_project_bwd_zeroed): v_means / v_quats / v_scales / v_opacities, means2d.grad, .absgrad and the gradient of
 extra colour channels are views of ONE region that the compositing backward clears beside its own work
 (mtgs_blend_bwd_packed(also_zero)); the projection backward writes the rows of the Gaussians that have a gradient to their places.

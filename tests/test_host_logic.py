@@ -332,3 +332,123 @@ def test_reduction_helpers_are_defined_once():
         assert count(name) == 1, name
     for name in (r"block_sum(_256)?", "dpp_perm", "sgn"):
         assert count(name) == 0, name
+
+
+# ---- the fused rasterization node: its backward plan, its input names, the colour-source protocol ----------------------------------
+_MTGS_BACKWARD = dict(packed=True, Cn=1, N=1001, n_vis=77, DC=3, absgrad=True, has_dp=False, info_grads=False, m2d_alive=True,
+                      m2d_retains=True, need_colors=False, open_channels=3, geometry_rows=False, want_grad_rows=False,
+                      prefill_enabled=True, zeroed_outputs=True)
+
+
+def test_backward_plan_of_the_mtgs_call():
+    """packed, one camera, visible Gaussians, absgrad, retain_grad() on means2d, deferred SH colours (3 open channels, nothing else)"""
+    from mtgs_amd.wrapper import _backward_plan
+    N = _MTGS_BACKWARD["N"]
+    p = _backward_plan(**_MTGS_BACKWARD)
+    assert p.zeroed is True and p.want_m2d and p.want_abs and not p.want_col and p.c0 == 3 and not p.rows_only and not p.geo_rows
+    assert list(p.views) == ["means", "quats", "scales", "opacities", "m2d", "abs"]
+    assert [v[2] for v in p.views.values()] == [(N, 3), (N, 4), (N, 3), (N,), (1, N, 2), (1, N, 2)]
+    pad4 = lambda n: -(-n // 4) * 4
+    at = 0
+    for name, (offset, count, shape) in p.views.items():      # N is odd: every count but the quaternions' needs padding
+        assert offset == at and offset % 4 == 0 and count == int(np.prod(shape)), name
+        at += pad4(count)
+    assert p.floats == at == sum(pad4(n) for n in (N * 3, N * 4, N * 3, N, N * 2, N * 2))
+    with pytest.raises(AttributeError):
+        p.zeroed = False      # immutable
+
+
+@pytest.mark.parametrize("change", [
+    dict(info_grads=True), dict(geometry_rows=True, want_grad_rows=True), dict(has_dp=True), dict(Cn=2), dict(n_vis=0), dict(N=0, n_vis=0),
+    dict(N=0), dict(prefill_enabled=False), dict(zeroed_outputs=False), dict(packed=False)],
+    ids=lambda c: "+".join(c))
+def test_backward_plan_without_the_zeroed_region(change):
+    from mtgs_amd.wrapper import _backward_plan
+    p = _backward_plan(**{**_MTGS_BACKWARD, **change})
+    assert p.zeroed is False and p.floats == 0 and p.views == {}
+    # the by-products do not depend on where they are written
+    assert p.want_m2d and p.c0 == 3 and not p.want_col
+    assert p.geo_rows == bool(change.get("geometry_rows")) and p.rows_only == bool(change.get("want_grad_rows"))
+    assert p.want_abs == (not p.rows_only)
+
+
+def test_backward_plan_by_products():
+    from mtgs_amd.wrapper import _backward_plan
+    plan = lambda **kw: _backward_plan(**{**_MTGS_BACKWARD, **kw})
+    N = _MTGS_BACKWARD["N"]
+    p = plan(want_grad_rows=True)      # the caller reads the compact rows: no dense absgrad
+    assert p.zeroed and p.rows_only and not p.want_abs and "abs" not in p.views and "m2d" in p.views
+    p = plan(m2d_retains=False)        # no retain_grad(): no means2d.grad, absgrad is still set on the tensor
+    assert p.zeroed and not p.want_m2d and "m2d" not in p.views and p.want_abs and "abs" in p.views
+    p = plan(m2d_alive=False, m2d_retains=False)      # the caller dropped info["means2d"]
+    assert p.zeroed and not p.want_m2d and not p.want_abs and list(p.views) == ["means", "quats", "scales", "opacities"]
+    assert not plan(absgrad=False).want_abs
+    for c0 in (0, 3, 6):
+        for extra in (1, 2):
+            p = plan(open_channels=c0, DC=c0 + extra, need_colors=True)
+            assert p.c0 == c0 and p.want_col and p.views["col"][1:] == (N * extra, (1, N, extra))
+            assert list(p.views)[-1] == "col" and p.floats == p.views["col"][0] + -(-N * extra // 4) * 4
+            assert not plan(open_channels=c0, DC=c0 + extra, need_colors=False).want_col
+        assert not plan(open_channels=c0, DC=c0, need_colors=True).want_col      # nothing beyond the source's own channels
+    # geometry rows need visible Gaussians and no gradient on info[...]
+    assert plan(geometry_rows=True).geo_rows and not plan(geometry_rows=True, n_vis=0).geo_rows
+    assert not plan(geometry_rows=True, info_grads=True).geo_rows
+
+
+def test_fused_input_names_agree_with_the_signature():
+    import inspect
+    from mtgs_amd import wrapper
+    params = list(inspect.signature(wrapper._FusedRasterization.forward).parameters.values())[1:]      # (without ctx)
+    assert tuple(p.name for p in params[:-1]) == wrapper._INPUTS
+    assert all(p.kind is inspect.Parameter.POSITIONAL_OR_KEYWORD for p in params[:-1])
+    assert params[-1].kind is inspect.Parameter.VAR_POSITIONAL
+    IN = wrapper._IN
+    assert [IN[n] for n in wrapper._INPUTS] == list(range(len(wrapper._INPUTS)))
+    assert IN["means"] == 0 and IN["colors"] == 4 and IN["viewmats"] == 5 and IN["backgrounds"] == 7
+    assert IN["campos"] == IN["sh_coeffs"] + 1 == len(wrapper._INPUTS) - 1      # ... then the var-positional tail
+
+    class Source:
+        n_nodes = 3
+    assert wrapper._tail_inputs(Source) == (IN["campos"] + 1, IN["campos"] + 3)
+    need = [False] * (len(wrapper._INPUTS) + 4)
+    assert not wrapper._needs_coeffs(need, Source)
+    need[IN["campos"] + 3] = True      # a direction tensor, not a coefficient tensor
+    assert not wrapper._needs_coeffs(need, Source)
+    need[IN["campos"] + 2] = True
+    assert wrapper._needs_coeffs(need, Source)
+
+    class Ctx:
+        needs_input_grad = need
+    got = wrapper._input_grads(Ctx, ("c1", None, "d0"), viewmats="vm", sh_coeffs="c0")
+    want = [None] * len(need)
+    want[5], want[20], want[22], want[24] = "vm", "c0", "c1", "d0"
+    assert got == tuple(want)
+    assert wrapper._input_grads(Ctx) == (None,) * len(need)
+
+
+def test_colour_source_and_exchange_protocol_defaults():
+    from mtgs_amd import wrapper
+    from mtgs_amd.appearance import WildColorSource
+    from mtgs_amd.dist import SparseGradExchange
+    from mtgs_amd.nodes import ColorSource
+    names = ("wild", "exchange", "autograd", "geometry_rows", "want_grad_rows", "touch_first", "camera_normals", "dirs", "dirs_inputs",
+             "wild_inputs", "n_nodes", "open_channels")
+    z = torch.zeros
+    cs = ColorSource(None, 2, 3, None, None, [])
+    ws = WildColorSource(z(4, 3), z(4, 15, 3), None, tuple(z(1) for _ in range(6)))
+    for src in (cs, ws):
+        for n in names:
+            assert hasattr(type(src), n) and hasattr(src, n), (type(src).__name__, n)
+        assert not (src.exchange or src.autograd or src.geometry_rows or src.want_grad_rows or src.touch_first)
+        assert src.camera_normals is None and src.dirs is None and src.dirs_inputs is None
+    assert cs.wild is False and cs.wild_inputs is None and cs.n_nodes == 2
+    assert ws.wild is True and len(ws.wild_inputs) == 9 and ws.n_nodes == 1
+    assert wrapper._open_channels(None) == 0
+    for src in (cs, ws):
+        assert src.open_channels == wrapper._open_channels(src) == 3
+        src.camera_normals = z(3, 4)
+        assert src.open_channels == wrapper._open_channels(src) == 6
+    assert SparseGradExchange.rows_hook is None and SparseGradExchange.zero_region is None
+    ex = SparseGradExchange(100, 16, "cpu")
+    assert ex.rows_hook is None and ex.zero_region is None and ex.rows.shape[1] == SparseGradExchange.ROW
+    assert wrapper._row_stride(1) == wrapper._row_stride(8) == 16 and wrapper._row_stride(9) == wrapper._row_stride(24) == 32

@@ -974,6 +974,38 @@ int mtgs_scale_reg_workspace_floats(int64_t n, size_t *nf);
 int mtgs_scale_reg_fwd(int64_t n, const float *scales, int two_d, float max_ratio, float *partials, float *out, void *stream);
 int mtgs_scale_reg_bwd(int64_t n, const float *scales, int two_d, float max_ratio, const float *v_out, float *v_scales, void *stream);
 
+/* ---- Pseudo-depth supervision of get_loss_dict (mtgs_scene_graph.py:844-873; mtgs/utils/geometric_loss.py:16-256) ----
+ * Additive block: MTGS_RAST_ABI_VERSION stays 28 and MTGS_RAST_HOT_ABI_VERSION 7 (no existing kernel or signature changes).
+ * Images are dense row-major: pred, gt [H, W] fp32, rgb [H, W, 3] fp32 (read by EDGE_AWARE_LOG_L1 only, otherwise nullable),
+ * mask a nullable [H, W] uint8 (0 = masked out).  m = (gt > lo) & (gt < hi) & mask (strict, fp32; HUBER_L1 also requires
+ * gt != 0), e = pred - gt, n = count(m).  The value of `kind` ("scalar" implementation of the reference):
+ *   MSE mean_m(e^2);  L1 mean_m |e|;  INVERSE_L1 mean_m |1 / (pred + 1e-6) - 1 / (gt + 1e-6)|;  LOG_L1 mean_m log(1 + |e|);
+ *   HUBER_L1 mean_m(|e| < d ? (e^2 + d^2) / (2 d) : |e|) with d = huber_thresh * max_m |e| (d = 0: every pixel takes |e|);
+ *   EDGE_AWARE_LOG_L1 sum_x / n_x + sum_y / n_y: exp(-mean_c |rgb[v,u,c] - rgb[v,u+1,c]|) log(1 + |e[v,u]|) over the selected
+ *   pixels with u < W - 1 (n_x of them), and the same towards v + 1 over those with v < H - 1 (n_y); the neighbour's mask and
+ *   depth are not read.
+ * mtgs_depth_loss_fwd: out[MTGS_DEPTH_LOSS_RECORD_FLOATS] = {loss, n, n_x, n_y, d, dL/dd, ties, max_m |e|} (the by-products
+ *   of the other kinds are 0).  n = 0: loss = 0.  n > 0 and n_x = 0 or n_y = 0: NaN (the mean of an empty tensor).  partials:
+ *   mtgs_depth_loss_workspace_floats floats (no initialisation).  One pass and a finish; HUBER_L1 two passes and two finishes.
+ * mtgs_depth_loss_bwd: v_pred [H, W] = v_out[0] * d loss / d pred by PyTorch's backward rules, EVERY pixel written (zero
+ *   outside m, when n = 0 and when v_out[0] = 0); `out` is the forward's record.  sgn(0) = sgn(NaN) = 0.  HUBER_L1: dL/dd =
+ *   (1/n) sum_{|e| < d} (1/2 - e^2 / (2 d^2)) goes, times huber_thresh, to the selected pixels with |e| = max_m |e|, shared
+ *   evenly among the `ties` of them (torch.max() over a whole tensor).
+ * Reductions: per-block partials, then a fixed-order fp64 sum; no float atomics (bitwise reproducible), no host reads and no
+ * allocation (graph-capturable).  The host checks name the bad argument (mtgs_rast_last_error). */
+#define MTGS_DEPTH_LOSS_MSE 0
+#define MTGS_DEPTH_LOSS_L1 1
+#define MTGS_DEPTH_LOSS_INVERSE_L1 2
+#define MTGS_DEPTH_LOSS_LOG_L1 3
+#define MTGS_DEPTH_LOSS_HUBER_L1 4
+#define MTGS_DEPTH_LOSS_EDGE_AWARE_LOG_L1 5
+#define MTGS_DEPTH_LOSS_RECORD_FLOATS 8
+int mtgs_depth_loss_workspace_floats(int width, int height, size_t *n);
+int mtgs_depth_loss_fwd(int kind, int width, int height, const float *pred, const float *gt, const uint8_t *mask, const float *rgb,
+                        float lo, float hi, float huber_thresh, float *partials, float *out, void *stream);
+int mtgs_depth_loss_bwd(int kind, int width, int height, const float *pred, const float *gt, const uint8_t *mask, const float *rgb,
+                        float lo, float hi, float huber_thresh, const float *v_out, const float *out, float *v_pred, void *stream);
+
 /* ---- seeding a node from a point cloud (mtgs_amd/csrc/seed.hip): VanillaGaussianSplattingModel.populate_modules
  * (vanilla_gaussian_splatting.py:114-196) without the host: sklearn's NearestNeighbors(n_neighbors = k + 1) with the first
  * column dropped (k_nearest_sklearn, :372-390), then scales, rotations, colours and opacities of every point in one kernel.

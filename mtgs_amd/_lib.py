@@ -161,6 +161,9 @@ _SIGNATURES = {
     "mtgs_scale_reg_workspace_floats": [_i64, C.POINTER(_sz)],
     "mtgs_scale_reg_fwd": [_i64, _vp, _i32, _f32, _vp, _vp, _vp],
     "mtgs_scale_reg_bwd": [_i64, _vp, _i32, _f32, _vp, _vp, _vp],
+    "mtgs_depth_loss_workspace_floats": [_i32, _i32, C.POINTER(_sz)],
+    "mtgs_depth_loss_fwd": [_i32, _i32, _i32, _vp, _vp, _vp, _vp, _f32, _f32, _f32, _vp, _vp, _vp],
+    "mtgs_depth_loss_bwd": [_i32, _i32, _i32, _vp, _vp, _vp, _vp, _f32, _f32, _f32, _vp, _vp, _vp, _vp],
     "mtgs_knn_workspace_bytes": [_i64, _i32, C.POINTER(_sz)],
     "mtgs_knn": [_i64, _i32, _vp, _i64, _vp, _vp, _vp, _vp, _sz, _vp],
     "mtgs_seed_fwd": [_i64, _i32, _vp, _vp, _vp, _i32, _i32, _vp, _vp, _vp, _i64, _vp, _vp],

@@ -26,10 +26,10 @@ COMMON_FLAGS = [
     "-Wall", "-Wno-unused-function", f"-I{PKG.parent / 'include'}",
 ]
 # The projection forward must round after every operation (bit-exact tile binning inputs); the metrics and the
-# geometric losses round as the reference's per-operation PyTorch kernels do, and so do the neighbour distances, the seeding
+# geometric and depth losses round as the reference's per-operation PyTorch kernels do, and so do the neighbour distances, the seeding
 # and the point-cloud filters (whose fp64 sums and voxel indices are compared bit for bit with a NumPy transcription).
 PER_FILE_FLAGS = {"project.hip": ["-ffp-contract=off"], "front.hip": ["-ffp-contract=off"], "metrics.hip": ["-ffp-contract=off"],
-                  "geomloss.hip": ["-ffp-contract=off"], "seed.hip": ["-ffp-contract=off"], "cloud.hip": ["-ffp-contract=off"]}
+                  "geomloss.hip": ["-ffp-contract=off"], "depthloss.hip": ["-ffp-contract=off"], "seed.hip": ["-ffp-contract=off"], "cloud.hip": ["-ffp-contract=off"]}
 
 
 class HipccNotFound(RuntimeError):

@@ -63,4 +63,6 @@ __device__ __forceinline__ int wave_max_i32(int v) {
     return v;
 }
 __device__ __forceinline__ int lane_id() { return (int)(threadIdx.x & 63); }
+// torch.abs's backward: grad * sgn(x) with sgn(0) = sgn(NaN) = 0
+__device__ __forceinline__ float sgn0(float d) { return d > 0.f ? 1.f : (d < 0.f ? -1.f : 0.f); }
 #endif

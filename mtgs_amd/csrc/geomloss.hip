@@ -55,9 +55,6 @@ __device__ __forceinline__ float3 target_normal(int W, int H, int u, int v, cons
     return make_float3((1.f + f0) / 2.f, (1.f + f1) / 2.f, (1.f + f2) / 2.f);
 }
 
-// torch.abs's backward: grad * sgn(x) with sgn(0) = sgn(NaN) = 0
-__device__ __forceinline__ float sgn0(float d) { return d > 0.f ? 1.f : (d < 0.f ? -1.f : 0.f); }
-
 __device__ __forceinline__ bool selected(float d, int64_t p, const uint8_t *__restrict__ mask, float lo, float hi) {
     return d > lo && d < hi && (mask == nullptr || mask[p] != 0);
 }

@@ -173,6 +173,95 @@ def inverse_depth_l1(depth: Tensor, gt_depth: Tensor, mask: Optional[Tensor] = N
     return _InverseDepthL1.apply(gt_depth, depth, mask, lo, hi, eps)
 
 
+_DEPTH_LOSS_KINDS = {"mse": 0, "L1": 1, "InverseL1": 2, "LogL1": 3, "HuberL1": 4, "EdgeAwareLogL1": 5}      # MTGS_DEPTH_LOSS_*
+_DEPTH_LOSS_RECORD = 8                                                                                    # MTGS_DEPTH_LOSS_RECORD_FLOATS
+
+
+class _PseudoDepthLoss(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, pred, gt, mask, rgb, kind, lo, hi, thresh):
+        require_gpu(pred, gt, mask, rgb)
+        H, W = pred.shape[:2]
+        p_c = _as_f32(pred, H, W)
+        g_c = _as_f32(gt, H, W)
+        m_c = _mask_u8(mask, H, W)
+        rgb_c = None if rgb is None else _as_f32(rgb, H, W, 3)
+        partials = workspace("mtgs_depth_loss_workspace_floats", W, H, device=pred.device, dtype=torch.float32)
+        out = torch.empty(_DEPTH_LOSS_RECORD, dtype=torch.float32, device=pred.device)
+        call("mtgs_depth_loss_fwd", kind, W, H, ptr(p_c), ptr(g_c), ptr(m_c), ptr(rgb_c), lo, hi, thresh, ptr(partials), ptr(out),
+             stream_of(pred))
+        ctx.save_for_backward(p_c, g_c, m_c, rgb_c, out)
+        ctx.cfg = (kind, H, W, lo, hi, thresh, pred.shape, pred.dtype)
+        return out[0]
+
+    @staticmethod
+    def backward(ctx, v_out):
+        p_c, g_c, m_c, rgb_c, out = ctx.saved_tensors
+        kind, H, W, lo, hi, thresh, shape, dtype = ctx.cfg
+        v = _cotangent(v_out)
+        v_pred = torch.empty_like(p_c)
+        call("mtgs_depth_loss_bwd", kind, W, H, ptr(p_c), ptr(g_c), ptr(m_c), ptr(rgb_c), lo, hi, thresh, ptr(v), ptr(out),
+             ptr(v_pred), stream_of(p_c))
+        return v_pred.reshape(shape).to(dtype), None, None, None, None, None, None, None
+
+
+def pseudo_depth_loss(pred_depth: Tensor, gt_depth: Tensor, mask: Optional[Tensor] = None, kind="EdgeAwareLogL1",
+                      rgb: Optional[Tensor] = None, lo: float = 0.1, hi: float = 50.0, huber_thresh: float = 0.2) -> Tensor:
+    """MTGS's depth term with depth_source = "pseudo" (mtgs/scene_model/mtgs_scene_graph.py:844-873), before depth_lambda:
+    the rendered depth against the dense monocular depth image batch["depth"], by the member of
+    mtgs/utils/geometric_loss.py:16-256 that `kind` names ("scalar" implementation, as the model constructs it).  With
+        m = (gt_depth > lo) & (gt_depth < hi) & mask        (strict, in fp32)
+        e = pred_depth - gt_depth over the n pixels of m
+    the value is
+        "mse"             mean(e^2)
+        "L1"              mean(|e|)
+        "InverseL1"       mean(|1 / (pred + 1e-6) - 1 / (gt + 1e-6)|)       (1e-6, not inverse_depth_l1's 1e-5)
+        "LogL1"           mean(log(1 + |e|))
+        "HuberL1"         d = huber_thresh * max|e|;  mean(where(|e| < d, (e^2 + d^2) / (2 d), |e|))     (also gt != 0)
+        "EdgeAwareLogL1"  sum(Lx) / n_x + sum(Ly) / n_y with Lx[v,u] = exp(-mean_c |rgb[v,u,c] - rgb[v,u+1,c]|) log(1 + |e[v,u]|)
+                          for u < W - 1 and Ly the same towards v + 1 for v < H - 1, both selected by m[v,u] alone (the
+                          neighbour's mask and depth are not read); rgb is the ground-truth image, as the reference passes it.
+    `kind` is one of these strings or the member of the reference's DepthLossType with that .value; "TV" and "EdgeAwareTV"
+    raise NotImplementedError (the reference cannot evaluate them through this call either).
+    pred_depth, gt_depth [H,W,1] / [H,W]; mask [H,W,1] / [H,W] bool or uint8, or None; rgb [H,W,3].  Returns a 0-dim fp32 tensor.
+
+    The selection is built inside the kernels and nothing is read back: no boolean-mask indexing, no `mask.sum() == 0` on the
+    host, so the term can be captured in a graph.  An empty selection gives 0 with a zero gradient (decided on the device).
+    "EdgeAwareLogL1" with n > 0 but n_x = 0 or n_y = 0 (a selection that lies only in the last column, say) is NaN, as torch's
+    mean of an empty tensor: pass it to combine_losses(..., drop_if_not_finite=...).  Differentiable with respect to
+    pred_depth only, by torch's rules: abs'(0) = 0; in "HuberL1" d is differentiable, and its gradient reaches the pixels
+    that attain max|e|, shared evenly among ties; d = 0 (every error exactly zero) gives 0 with a zero gradient, not NaN.
+    One pass and a finish forward ("HuberL1": two of each), one launch backward, bitwise reproducible.
+
+    Parity-unpinned, like the rest of the loss head: the reference module cannot be imported where the tests run (it needs
+    cv2 and torchmetrics), so the pin is the float64 restatement of these formulas in tests/depth_loss_refs.py."""
+    kind = getattr(kind, "value", kind)
+    if kind in ("TV", "EdgeAwareTV"):
+        raise NotImplementedError(f"pseudo_depth_loss: depth loss kind {kind!r} is not implemented (its forward does not take "
+                                  "(pred[mask], gt[mask]))")
+    if kind not in _DEPTH_LOSS_KINDS:
+        raise ValueError(f"pseudo_depth_loss: unknown depth loss kind {kind!r}; expected one of {sorted(_DEPTH_LOSS_KINDS)}")
+    assert pred_depth.dim() in (2, 3) and pred_depth.numel() == pred_depth.shape[0] * pred_depth.shape[1], pred_depth.shape
+    H, W = pred_depth.shape[:2]
+    assert gt_depth.dim() in (2, 3) and gt_depth.numel() == H * W and tuple(gt_depth.shape[:2]) == (H, W), (pred_depth.shape, gt_depth.shape)
+    if mask is not None:
+        assert mask.numel() == H * W and tuple(mask.shape[:2]) == (H, W), mask.shape
+        assert mask.dtype in (torch.bool, torch.uint8), mask.dtype
+    if kind == "EdgeAwareLogL1":
+        if rgb is None:
+            raise ValueError("pseudo_depth_loss: kind 'EdgeAwareLogL1' needs rgb (the ground-truth image)")
+        assert tuple(rgb.shape) == (H, W, 3), rgb.shape
+        if rgb.requires_grad:
+            raise NotImplementedError("pseudo_depth_loss: gradient with respect to rgb is not implemented")
+    else:
+        rgb = None
+    if gt_depth.requires_grad:
+        raise NotImplementedError("pseudo_depth_loss: gradient with respect to gt_depth is not implemented")
+    if kind == "HuberL1" and not (huber_thresh > 0 and np.isfinite(huber_thresh)):
+        raise ValueError(f"pseudo_depth_loss: huber_thresh must be finite and > 0 (got {huber_thresh})")
+    return _PseudoDepthLoss.apply(pred_depth, gt_depth, mask, rgb, _DEPTH_LOSS_KINDS[kind], float(lo), float(hi), float(huber_thresh))
+
+
 class _Combine(torch.autograd.Function):
     @staticmethod
     def forward(ctx, stacked, weights, guard_mask, constant):

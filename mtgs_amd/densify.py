@@ -15,6 +15,7 @@ import numpy as np
 import torch
 from torch import Tensor
 
+from ._abi import struct_dtype
 from ._lib import call, ptr, require_gpu, stream_of
 
 
@@ -41,8 +42,7 @@ def update_statistics(xys_grad_norm: Tensor, vis_counts: Tensor, max_2Dsize: Ten
          ptr(max_2Dsize), stream_of(xys_grad_norm))
 
 
-_STATS_DESC = np.dtype([("n", "<i8"), ("first_block", "<i8"), ("start", "<i8"), ("xys_grad_norm", "<u8"), ("vis_counts", "<u8"),
-                        ("max_2dsize", "<u8")], align=True)
+_STATS_DESC = struct_dtype("mtgs_stats_desc")      # include/mtgs_rast.h
 
 
 @torch.no_grad()

@@ -19,6 +19,8 @@ import numpy as np
 import torch
 import torch.distributed as dist
 
+from ._abi import struct_dtype
+
 
 def init_from_env(backend: Optional[str] = None, timeout_s: Optional[float] = None) -> tuple:
     """Initialises torch.distributed from RANK / LOCAL_RANK / WORLD_SIZE / MASTER_* (torchrun).
@@ -130,11 +132,8 @@ def all_reduce_grads(params: Sequence[torch.Tensor], average: bool = False, grou
     return nbytes
 
 
-_DP_GROUP = np.dtype([("mask", "<u8"), ("coef_rows", "<u8"), ("coef_words", "<u8"), ("coef_prefix", "<u8"), ("coef_row_of", "<u8"),
-                      ("coef_cap", "<i8")])       # include/mtgs_rast.h: mtgs_dp_group
-
-
-_DP_CHUNKS = np.dtype([("n", "<i4"), ("_pad", "<i4"), ("begin", "<i8", (17,)), ("rows", "<u8", (16,)), ("cap", "<i8", (16,))])   # mtgs_dp_chunks
+_DP_GROUP = struct_dtype("mtgs_dp_group")       # include/mtgs_rast.h
+_DP_CHUNKS = struct_dtype("mtgs_dp_chunks")
 
 
 class SparseGradExchange:

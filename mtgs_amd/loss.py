@@ -15,6 +15,7 @@ import numpy as np
 import torch
 from torch import Tensor
 
+from ._abi import constant, struct_dtype
 from ._lib import call, ptr, require_gpu, stream_of, workspace
 
 
@@ -173,8 +174,9 @@ def inverse_depth_l1(depth: Tensor, gt_depth: Tensor, mask: Optional[Tensor] = N
     return _InverseDepthL1.apply(gt_depth, depth, mask, lo, hi, eps)
 
 
-_DEPTH_LOSS_KINDS = {"mse": 0, "L1": 1, "InverseL1": 2, "LogL1": 3, "HuberL1": 4, "EdgeAwareLogL1": 5}      # MTGS_DEPTH_LOSS_*
-_DEPTH_LOSS_RECORD = 8                                                                                    # MTGS_DEPTH_LOSS_RECORD_FLOATS
+_DEPTH_LOSS_KINDS = {name: constant("MTGS_DEPTH_LOSS_" + macro) for name, macro in (
+    ("mse", "MSE"), ("L1", "L1"), ("InverseL1", "INVERSE_L1"), ("LogL1", "LOG_L1"), ("HuberL1", "HUBER_L1"), ("EdgeAwareLogL1", "EDGE_AWARE_LOG_L1"))}
+_DEPTH_LOSS_RECORD = constant("MTGS_DEPTH_LOSS_RECORD_FLOATS")
 
 
 class _PseudoDepthLoss(torch.autograd.Function):
@@ -364,8 +366,7 @@ def output_head(render: Tensor, alpha: Tensor, background: Tensor, exposure: Opt
     return _OutputHead.apply(render, alpha, background, exposure, bool(depth), int(normal_channel))
 
 
-_OOB_DESC = np.dtype([("n", "<i8"), ("first_block", "<i8"), ("start", "<i8"), ("means", "<u8"), ("opacities", "<u8"),
-                      ("g_opacities", "<u8"), ("limit", "<f4", (3,)), ("reserved", "<f4")], align=True)
+_OOB_DESC = struct_dtype("mtgs_oob_desc")      # include/mtgs_rast.h
 
 
 class _OobLoss(torch.autograd.Function):

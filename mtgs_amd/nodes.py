@@ -21,6 +21,7 @@ import numpy as np
 import torch
 from torch import Tensor
 
+from ._abi import struct_dtype
 from ._lib import call, host_i64, ptr, require_gpu, stream_of
 
 
@@ -134,16 +135,7 @@ _NODE_KEYS = ("means", "scales", "quats", "opacities", "features_dc", "features_
 _NK = len(_NODE_KEYS)
 
 
-# mtgs_node_desc of include/mtgs_rast.h (checked against mtgs_node_desc_bytes() on first use)
-_DESC = np.dtype([(k, "<i8") for k in ("n", "first_block", "start")]
-                 + [(k, "<u8") for k in ("means", "scales_raw", "quats_raw", "opacities_raw", "features_dc", "features_dc_add",
-                                         "features_rest")]
-                 + [(k, "<i8") for k in ("dc_stride", "dc_add_stride", "rest_stride")] + [("pose", "<u8"), ("pose_trans", "<u8")]
-                 + [(k, "<i4") for k in ("k_rest", "use_sh", "n_traversals", "traversal", "pose_normalize", "skip_colors")]
-                 + [(k, "<u8") for k in ("scales", "quats", "opacities", "rgbs", "clamp_mask", "means_out", "v_scales", "v_quats",
-                                         "v_opacities", "v_rgbs", "v_means", "g_scales_raw", "g_quats_raw", "g_opacities_raw",
-                                         "g_features_dc", "g_features_rest", "g_features_dc_add", "g_means", "g_pose", "g_pose_quat_row",
-                                         "g_pose_trans_row", "frame_dev")], align=True)
+_DESC = struct_dtype("mtgs_node_desc")     # include/mtgs_rast.h (checked against mtgs_node_desc_bytes() of the loaded library on first use)
 _desc_checked = False
 
 

@@ -47,15 +47,10 @@ from typing import Optional
 import numpy as np
 import torch
 
+from ._abi import constant, struct_dtype
 from ._lib import call, load, ptr, stream_of
 
-_GROUP = np.dtype([("p", "<u8"), ("m", "<u8"), ("v", "<u8"), ("g", "<u8"), ("rows", "<u8"), ("row_of", "<u8"), ("catchup", "<u8"),
-                   ("last", "<u8"), ("hist", "<u8"), ("row_ids", "<u8"), ("row_count_dev", "<u8"), ("caught", "<u8"), ("sub_index_dev", "<u8"), ("row_flags", "<u8"),
-                   ("n", "<i8"), ("first_block", "<i8"), ("row_stride", "<i8"), ("caught_stride", "<i8"), ("item_start", "<i8"), ("n_rows", "<i8"),
-                   ("width", "<i4"), ("row_col", "<i4"),
-                   ("vec_ok", "<i4"), ("sub_width", "<i4"), ("sub_index", "<i4"), ("mode", "<i4"), ("catchup_k", "<i4"),
-                   ("hyper_index", "<i4"), ("caught_col", "<i4"), ("rank_start", "<i4"), ("rank_count", "<i4"), ("zero_probe", "<i4"), ("one_minus_beta1", "<f4"), ("beta2", "<f4"), ("one_minus_beta2", "<f4"), ("eps", "<f4"),
-                   ("weight_decay", "<f4"), ("grad_scale", "<f4")], align=True)
+_GROUP = struct_dtype("mtgs_adam_group")      # include/mtgs_rast.h (checked against mtgs_adam_group_bytes() of the loaded library on first use)
 
 
 def _put_slice(r, t) -> None:
@@ -69,7 +64,8 @@ def _put_slice(r, t) -> None:
         r["sub_index"], r["sub_index_dev"] = int(t), 0
 
 
-MODE_DENSE, MODE_SLICE, MODE_ROWS_CATCHUP, MODE_ROWS_STEP, MODE_ROWS_FLUSH, MODE_ROWS_PEEK = 0, 1, 2, 3, 4, 5   # MTGS_ADAM_*
+MODE_DENSE, MODE_SLICE, MODE_ROWS_CATCHUP, MODE_ROWS_STEP, MODE_ROWS_FLUSH, MODE_ROWS_PEEK = (
+    constant("MTGS_ADAM_" + k) for k in ("DENSE", "SLICE", "ROWS_CATCHUP", "ROWS_STEP", "ROWS_FLUSH", "ROWS_PEEK"))
 _checked = False
 
 

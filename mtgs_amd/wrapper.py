@@ -23,6 +23,7 @@ import torch
 from torch import Tensor
 
 from . import _lib
+from ._abi import constant
 from ._lib import call, host_i64, ptr, require_gpu, stream_of
 
 SUPPORTED_CHANNELS = (1, 2, 3, 4, 5, 6, 7, 8, 16, 32)
@@ -797,6 +798,10 @@ class _RasterizeToPixels(torch.autograd.Function):
 # ------------------------------------------------------------------------------------- fused path
 TILE_SIZE = 16           # the tile edge of the fused path (pixels)
 RECORD_CHANNELS = 8      # blended channels a packed record holds (csrc/raster_rec.hpp)
+# include/mtgs_rast.h: the flag bits of mtgs_bin3_build; visible Gaussians per workgroup of mtgs_vis_color_* (the granularity of dir_part)
+_BIN3_TIGHT, _BIN3_FILL_TO_M, _BIN3_FILL_TO_CAP, _BIN3_PREZEROED, _BIN3_STATUS = (
+    constant("MTGS_BIN3_" + k) for k in ("TIGHT", "FILL_TO_M", "FILL_TO_CAP", "PREZEROED", "STATUS"))
+_VIS_COLOR_ROWS = constant("MTGS_VIS_COLOR_ROWS")
 speculative_sizing = True  # enqueue binning + compositing before the host knows (n_vis, M); see _SizePlan
 _force_caps = None       # tests: (cap_vis, cap_M) used for the speculative attempt, to exercise the overflow path
 _debug_rows = None       # tests: a dict that the fused backward fills with its compact gradient rows {"G", "vis_ids", "DC"}
@@ -1020,12 +1025,13 @@ def _packed_path(ins, dims, outs, need, dp, cs):
     # colours, and one pass of the compositing DECISIONS (mtgs_blend_touch_packed) flags the Gaussians the frame composites
     # from -- a few percent of the visible ones in an opaque scene.  Peek, SH evaluation and normals work on those alone.
     touch_first = cs is not None and bool(cs.touch_first)
-    # tile lists of this frame (thread-local mode, read once): gsplat's by default; mtgs_bin3_build flags: 1 = tight lists,
-    # 2 = sentinel-fill the tail [n_listed, M) of flatten_ids / isect_ids (tight lists, tensors sliced to gsplat's M),
-    # 4 = sentinel-fill up to the capacity (graph mode: the tensors are capacity-sized in both list modes), 16 = the frame's
-    # counts and its overflow flag as device words behind `totals` (graph mode)
+    # tile lists of this frame (thread-local mode, read once): gsplat's by default; mtgs_bin3_build flags: TIGHT lists,
+    # FILL_TO_M = sentinel-fill the tail [n_listed, M) of flatten_ids / isect_ids (tight lists, tensors sliced to gsplat's M),
+    # FILL_TO_CAP = sentinel-fill up to the capacity (graph mode: the tensors are capacity-sized in both list modes), STATUS = the
+    # frame's counts and its overflow flag as device words behind `totals` (graph mode)
     tight = lists_are_tight()
-    list_flags = (1 if tight else 0) | (4 | 16 if graph_caps is not None else (2 if tight else 0))
+    list_flags = (_BIN3_TIGHT if tight else 0) | (_BIN3_FILL_TO_CAP | _BIN3_STATUS if graph_caps is not None
+                                                  else (_BIN3_FILL_TO_M if tight else 0))
 
     def colours(b, flags):   # colours of the visible Gaussians, straight into their records
         cap_vis = b.cap_vis
@@ -1077,7 +1083,7 @@ def _packed_path(ins, dims, outs, need, dp, cs):
         call("mtgs_bin3_build", Cn, N, TILE_SIZE, tw, th, ptr(totals), b.cap_vis, cap_M, ptr(b.recs),
              ptr(b.vis_ids), ptr(b.vis_keys), ptr(out.rank_ids),
              ptr(out.flatten_ids), ptr(out.isect_ids), ptr(offsets_buf), ptr(order),
-             list_flags | (8 if prezeroed is not None else 0), ws_ptr, ws_bytes, st)
+             list_flags | (_BIN3_PREZEROED if prezeroed is not None else 0), ws_ptr, ws_bytes, st)
         if touch_first:
             flags = torch.empty(max(b.cap_vis, 1), dtype=torch.uint8, device=dev)
             call("mtgs_blend_touch_packed", Cn, ptr(b.recs), width, height, tw, th, ptr(offsets_buf), ptr(out.rank_ids),
@@ -1353,7 +1359,7 @@ class _FusedRasterization(torch.autograd.Function):
             if not (cs.autograd and cs.dirs is not None and not (need_coef or need_dirs)):      # (frozen coefficients: nothing to do)
                 feat = torch.empty((max(n_vis, 1), 48), dtype=torch.float32, device=dev) if dense_coeffs is None else None
                 dir_rows = torch.empty((max(n_vis, 1), 3), dtype=torch.float32, device=dev) if want_dirs else None
-                dir_part = torch.zeros((-(-max(n_vis, 1) // 64), 3), dtype=torch.float32, device=dev) if want_dirs else None      # (MTGS_VIS_COLOR_ROWS)
+                dir_part = torch.zeros((-(-max(n_vis, 1) // _VIS_COLOR_ROWS), 3), dtype=torch.float32, device=dev) if want_dirs else None
                 call("mtgs_vis_color_bwd_dirs", cs.n_nodes, ptr(cs.table), cs.degree, ptr(cs.cam), ptr(means), ptr(vis_ids), ptr(totals),
                      n_vis, ptr(G), RS, 8, ptr(recs), ptr(ctx.vis_mask), ptr(feat), ptr(dir_rows), ptr(dir_part), ptr(dense_coeffs),
                      ptr(cs.dirs), st)

@@ -33,7 +33,8 @@ def test_wild_symbols_declared_bound_and_exported(hip_lib):
         assert name in syms, name
         assert name in _lib.EXPORTS, name
         assert hasattr(hip_lib, name), name
-    assert hip_lib.mtgs_rast_version() == 28 and hip_lib.mtgs_rast_hot_version() == 7
+    abi, hot = (int(re.search(r"#define %s (\d+)" % macro, text).group(1)) for macro in ("MTGS_RAST_ABI_VERSION", "MTGS_RAST_HOT_ABI_VERSION"))
+    assert hip_lib.mtgs_rast_version() == abi and hip_lib.mtgs_rast_hot_version() == hot
 
 
 def test_wild_host_validation_names_the_null_pointer(hip_lib):

@@ -33,6 +33,8 @@
 #include <stddef.h>
 #include <stdint.h>
 
+#include "mtgs_crop.h"   /* additive block of its own: the crop box (mtgs_crop_select, mtgs_crop_gather) */
+
 #ifdef __cplusplus
 extern "C" {
 #endif

@@ -11,9 +11,11 @@ Beyond gsplat's surface: `mtgs_amd.graph_mode` / `mtgs_amd.graphs.GraphedIterati
 / `.densify` / `.optim` (the fused neighbours of the path), `mtgs_amd.appearance` (WildGaussians.py's appearance colours: `wild_colors`,
 `wild_color_source`), `mtgs_amd.metrics` (get_metrics_dict's image metrics: `color_correct`, `image_metrics`), `mtgs_amd.seed`
 (populate_modules: a node from a point cloud -- `knn_distances`, `seed_gaussians`, `sky_points`), `mtgs_amd.pointcloud`
-(_load_3D_points: the cloud that node is seeded from -- `statistical_outlier_removal`, `voxel_down_sample`, `prepare_seed_cloud`).
+(_load_3D_points: the cloud that node is seeded from -- `statistical_outlier_removal`, `voxel_down_sample`, `prepare_seed_cloud`),
+`mtgs_amd.crop` (the viewer's and the render tool's crop box: `OrientedBox`, `crop_gaussians`).
 """
 from .appearance import wild_color_source, wild_colors
+from .crop import OrientedBox, crop_gaussians
 from .metrics import color_correct, image_metrics
 from .pointcloud import prepare_seed_cloud, statistical_outlier_removal, voxel_down_sample
 from .rendering import rasterization
@@ -25,4 +27,4 @@ __version__ = "0.1.0"
 __all__ = ["rasterization", "spherical_harmonics", "fully_fused_projection", "isect_tiles",
            "isect_offset_encode", "rasterize_to_pixels", "graph_mode", "exact_lists", "tight_lists", "lists_are_tight", "sh_prefill", "sh_lazy",
            "wild_colors", "wild_color_source", "color_correct", "image_metrics", "knn_distances", "seed_gaussians", "sky_points",
-           "statistical_outlier_removal", "voxel_down_sample", "prepare_seed_cloud"]
+           "statistical_outlier_removal", "voxel_down_sample", "prepare_seed_cloud", "OrientedBox", "crop_gaussians"]

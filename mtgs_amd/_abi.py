@@ -4,6 +4,7 @@
     signatures()        {name: (result letter, argument letters)}: the same, as tests/golden/abi_signatures.txt spells it
     struct_dtype(name)  numpy record dtype of `typedef struct name { ... } name;` with C's natural alignment
     constant(name)      value of a #define (an integer or a float) or of an enumerator of an anonymous enum
+    extension_prototypes(), extension_signatures()   the same two tables for the headers mtgs_rast.h includes (EXTENSION_HEADERS)
 
 A few regular expressions over a header this project owns, not a C parser: anything they do not recognise raises with the line
 number and the text of the declaration -- nothing is skipped or guessed.  If a new header line resists, write it in the plain form
@@ -20,6 +21,9 @@ from typing import NamedTuple
 import numpy as np
 
 HEADER = Path(__file__).resolve().parent.parent / "include" / "mtgs_rast.h"
+# additive blocks that are headers of their own (mtgs_rast.h includes them): read by the same parser, bound by _lib.load() like
+# the rest, kept apart from prototypes() / signatures(), which describe mtgs_rast.h's own text
+EXTENSION_HEADERS = ("mtgs_crop.h",)
 
 # by-value scalars: C type -> (ctypes type, numpy format, letter of tests/golden/abi_signatures.txt)
 _SCALARS = {"int": (C.c_int, "<i4", "i"), "int32_t": (C.c_int, "<i4", "i"), "int64_t": (C.c_int64, "<i8", "l"),
@@ -138,8 +142,27 @@ def _header() -> Abi:
     return parse(HEADER.read_text())
 
 
+@lru_cache(maxsize=None)
+def _extensions() -> Abi:
+    abi = Abi({}, {}, {}, {})
+    for name in EXTENSION_HEADERS:
+        part = parse((HEADER.parent / name).read_text())
+        for mine, theirs in zip(abi, part):
+            mine.update(theirs)
+    return abi
+
+
 def prototypes() -> dict:
     return _header().prototypes
+
+
+def extension_prototypes() -> dict:
+    """{name: (restype, [argtypes])} of the entry points the EXTENSION_HEADERS declare"""
+    return _extensions().prototypes
+
+
+def extension_signatures() -> dict:
+    return _extensions().signatures
 
 
 def signatures() -> dict:

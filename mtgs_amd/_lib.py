@@ -25,9 +25,12 @@ def use_library(path) -> None:
         raise RuntimeError("use_library() after the library was loaded")
     LIB_PATH = Path(path)
 
-# include/mtgs_rast.h is the description of the ABI: argument and result types of every entry point are read from its prototypes
+# include/mtgs_rast.h (and the headers it includes, below) is the description of the ABI: argument and result types of every entry
+# point are read from its prototypes
 _PROTOTYPES = _abi.prototypes()
 EXPORTS = list(_PROTOTYPES)
+_EXTENSION_PROTOTYPES = _abi.extension_prototypes()     # the headers mtgs_rast.h includes (include/mtgs_crop.h)
+EXTENSION_EXPORTS = list(_EXTENSION_PROTOTYPES)
 ABI_VERSION = _abi.constant("MTGS_RAST_ABI_VERSION")
 HOT_ABI_VERSION = _abi.constant("MTGS_RAST_HOT_ABI_VERSION")      # hot-path subset: what profiles/rNN_pmc_step.json is keyed on
 
@@ -44,7 +47,7 @@ def load() -> C.CDLL:
             f"{LIB_PATH} is missing: build it with `python -m mtgs_amd.build` (needs hipcc). "
             "mtgs_amd has no CPU or PyTorch fallback for the rasterizer.")
     lib = C.CDLL(str(LIB_PATH))
-    for name, (restype, argtypes) in _PROTOTYPES.items():
+    for name, (restype, argtypes) in {**_PROTOTYPES, **_EXTENSION_PROTOTYPES}.items():
         fn = getattr(lib, name)
         fn.argtypes = argtypes
         fn.restype = restype

@@ -27,9 +27,11 @@ COMMON_FLAGS = [
 ]
 # The projection forward must round after every operation (bit-exact tile binning inputs); the metrics and the
 # geometric and depth losses round as the reference's per-operation PyTorch kernels do, and so do the neighbour distances, the seeding
-# and the point-cloud filters (whose fp64 sums and voxel indices are compared bit for bit with a NumPy transcription).
+# and the point-cloud filters (whose fp64 sums and voxel indices are compared bit for bit with a NumPy transcription); the crop box
+# decides a row by three fp32 dot products that the host evaluates operation by operation in torch and NumPy.
 PER_FILE_FLAGS = {"project.hip": ["-ffp-contract=off"], "front.hip": ["-ffp-contract=off"], "metrics.hip": ["-ffp-contract=off"],
-                  "geomloss.hip": ["-ffp-contract=off"], "depthloss.hip": ["-ffp-contract=off"], "seed.hip": ["-ffp-contract=off"], "cloud.hip": ["-ffp-contract=off"]}
+                  "geomloss.hip": ["-ffp-contract=off"], "depthloss.hip": ["-ffp-contract=off"], "seed.hip": ["-ffp-contract=off"], "cloud.hip": ["-ffp-contract=off"],
+                  "crop.hip": ["-ffp-contract=off"]}
 
 
 class HipccNotFound(RuntimeError):
@@ -59,7 +61,7 @@ def stale_sources():
     if not LIB.exists():
         return sources()
     t = LIB.stat().st_mtime
-    deps = sources() + list(CSRC.glob("*.hpp")) + [PKG.parent / "include" / "mtgs_rast.h"]
+    deps = sources() + list(CSRC.glob("*.hpp")) + sorted((PKG.parent / "include").glob("*.h"))
     return [d for d in deps if d.stat().st_mtime > t]
 
 
@@ -70,7 +72,7 @@ def build(force: bool = False, verbose: bool = False) -> Path:
     for stale in OBJ.glob("*.o"):          # objects of sources that no longer exist (bin2.o after round 2)
         if stale.stem not in live:
             stale.unlink()
-    headers = list(CSRC.glob("*.hpp")) + [PKG.parent / "include" / "mtgs_rast.h", Path(__file__)]
+    headers = list(CSRC.glob("*.hpp")) + sorted((PKG.parent / "include").glob("*.h")) + [Path(__file__)]
     jobs = []
     for src in sources():
         obj = OBJ / (src.stem + ".o")

@@ -74,7 +74,7 @@ def collect_gaussians(nodes: Mapping[str, Mapping[str, Tensor]], camera_to_world
                       frame_idx: Optional[int] = None, timestamp: Optional[float] = None,
                       frame_timestamps: Optional[Tensor] = None, fourier: Optional[Mapping] = None,
                       instance_heights: Optional[Mapping[str, float]] = None, deform_time: Optional[float] = None,
-                      undeformed: bool = False) -> Dict[str, Tensor]:
+                      undeformed: bool = False, crop_box=None) -> Dict[str, Tensor]:
     """means / scales / quats / opacities / rgbs / model_id of the listed nodes, activated by
     mtgs_amd.nodes.node_gaussians and concatenated in order (MTGSSceneModel.get_gaussians,
     mtgs_scene_graph.py:408-461).  Multi-colour nodes need `traversal_index` (get_pertravel_features,
@@ -89,7 +89,9 @@ def collect_gaussians(nodes: Mapping[str, Mapping[str, Tensor]], camera_to_world
     the interpolation FRACTION, deformable_node.py:190) and `instance_heights[name]` (instance_size[2], kept outside the state
     dict).  The reference applies the network whenever step > use_deformgs_after (deformable_node.py:230-232), so a trained
     checkpoint rendered without them would be rendered WRONGLY: that raises unless `undeformed=True` asks for the canonical
-    geometry explicitly."""
+    geometry explicitly.
+    crop_box (mtgs_amd.crop.OrientedBox): only the Gaussians whose means lie inside are returned (mtgs_scene_graph.py:457-459;
+    `mtgs_amd.crop.crop_gaussians` of the result, so without "node_table").  Evaluation only: call it under torch.no_grad()."""
     from .deform import deformation_from_state
     from .nodes import cam_obj_yaw, collect_gaussians as _collect, fourier_features_dc, object_pose
     names = list(nodes.keys()) if node_names is None else list(node_names)
@@ -154,4 +156,7 @@ def collect_gaussians(nodes: Mapping[str, Mapping[str, Tensor]], camera_to_world
             parts += [out["scales"][at:s0], out["scales"][s0:s0 + d.shape[0]] + d]
             at = s0 + d.shape[0]
         out["scales"] = torch.cat(parts + [out["scales"][at:]])
+    if crop_box is not None:
+        from .crop import crop_gaussians
+        out = crop_gaussians(out, crop_box)
     return out

@@ -578,7 +578,7 @@ class _CollectNodes(torch.autograd.Function):
 
 
 def collect_gaussians(nodes, camera_to_worlds: Tensor, sh_degree_to_use: int, model_sh_degree: int = 3,
-                      raw_colors: bool = False, deferred_colors: bool = False) -> Dict[str, Tensor]:
+                      raw_colors: bool = False, deferred_colors: bool = False, crop_box=None) -> Dict[str, Tensor]:
     """MTGSSceneModel.get_gaussians for static nodes (/root/reference/mtgs/scene_model/mtgs_scene_graph.py:408-461): the
     activated Gaussians of every node, concatenated in order, plus `model_id`.  `nodes` is a sequence of dicts of RAW
     parameters {"means", "scales", "quats", "opacities", "features_dc", "features_rest"} with, for multi-colour nodes,
@@ -596,7 +596,13 @@ def collect_gaussians(nodes, camera_to_worlds: Tensor, sh_degree_to_use: int, mo
     "color_source" (ColorSource) makes `rasterization(..., color_source=...)` evaluate SH + clamp for the Gaussians its
     projection found visible, straight into their records; the coefficient gradient comes back as compact rows
     (ColorSource.apply_to(FusedAdam)).  MTGS computes the colours of all Gaussians of all nodes every step
-    (vanilla_gaussian_splatting.py:309-322); a camera sees ~15 % of them."""
+    (vanilla_gaussian_splatting.py:309-322); a camera sees ~15 % of them.
+    crop_box (mtgs_amd.crop.OrientedBox): the viewer's / render tool's crop (mtgs_scene_graph.py:457-459) -- the result is
+    `mtgs_amd.crop.crop_gaussians(result, crop_box)`: only the Gaussians whose means lie inside, without "node_table".  Evaluation
+    only (call it under torch.no_grad()), and not with deferred_colors."""
+    if crop_box is not None and deferred_colors:
+        raise NotImplementedError("collect_gaussians: crop_box with deferred_colors=True: the colour kernels of the visible rows address "
+                                  "the Gaussians through the node table, which a crop invalidates -- collect with deferred_colors=False")
     specs, flat, sizes = [], [], []
     use_sh = model_sh_degree > 0
     assert use_sh or not raw_colors, "raw_colors needs an SH colour model"
@@ -664,6 +670,9 @@ def collect_gaussians(nodes, camera_to_worlds: Tensor, sh_degree_to_use: int, mo
         cs.node_params = [(st, n, nd["features_dc"], nd.get("features_adapters"), nd["features_rest"], nd.get("traversal_index"))
                           for (st, n), nd in zip(cs.node_params, nodes)]
         out["color_source"] = cs
+    if crop_box is not None:
+        from .crop import crop_gaussians
+        out = crop_gaussians(out, crop_box)
     return out
 
 

@@ -34,6 +34,7 @@
 #include <stdint.h>
 
 #include "mtgs_crop.h"   /* additive block of its own: the crop box (mtgs_crop_select, mtgs_crop_gather) */
+#include "mtgs_refine_scene.h"   /* additive block of its own: refinement_after for a whole scene graph in one pass */
 
 #ifdef __cplusplus
 extern "C" {

@@ -5,6 +5,7 @@
     struct_dtype(name)  numpy record dtype of `typedef struct name { ... } name;` with C's natural alignment
     constant(name)      value of a #define (an integer or a float) or of an enumerator of an anonymous enum
     extension_prototypes(), extension_signatures()   the same two tables for the headers mtgs_rast.h includes (EXTENSION_HEADERS)
+    header_abi(name)    the whole Abi tuple (prototypes, signatures, structs, constants) of ONE named header that mtgs_rast.h includes
 
 A few regular expressions over a header this project owns, not a C parser: anything they do not recognise raises with the line
 number and the text of the declaration -- nothing is skipped or guessed.  If a new header line resists, write it in the plain form
@@ -150,6 +151,16 @@ def _extensions() -> Abi:
         for mine, theirs in zip(abi, part):
             mine.update(theirs)
     return abi
+
+
+@lru_cache(maxsize=None)
+def header_abi(name: str) -> Abi:
+    """What the included header include/`name` declares by itself: the same Abi tuple as for mtgs_rast.h, structs and constants
+    included.  For additive blocks that keep a reviewed record of their own (include/mtgs_refine_scene.h) and are no part of
+    EXTENSION_HEADERS."""
+    if not any(re.fullmatch(r'#\s*include\s+"%s".*' % re.escape(name), line.strip()) for line in HEADER.read_text().splitlines()):
+        raise ValueError(f"{HEADER.name} does not include {name!r}")
+    return parse((HEADER.parent / name).read_text())
 
 
 def prototypes() -> dict:

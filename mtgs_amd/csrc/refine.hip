@@ -27,6 +27,7 @@ struct RefineCfg {
     float grad_thresh, size_thresh, split_screen_size, cull_alpha_thresh, cull_scale_thresh, cull_screen_size;
     int nsamps, use_screen_split, cull_big, cull_screen, clone_sample_means;
     uint32_t seed_lo, seed_hi, step;
+    float far_radius, far_factor;   // cull rule: beyond |mean| > far_radius the size limit is far_factor * cull_scale_thresh
 };
 constexpr int MAX_SAMPS = 4;
 constexpr float kSplitShrink = 1.6f;
@@ -68,8 +69,8 @@ __device__ __forceinline__ float max_exp(const float (&sl)[3]) { return fmaxf(fm
 __device__ __forceinline__ bool culled(const RefineCfg &c, const float (&m)[3], const float (&sl)[3], float opacity_logit, float max2d) {
     bool cull = 1.0f / (1.0f + expf(-opacity_logit)) < c.cull_alpha_thresh;
     if (c.cull_big) {
-        const bool far = sqrtf(m[0] * m[0] + m[1] * m[1] + m[2] * m[2]) > 100.f;
-        cull = cull || max_exp(sl) > (far ? 40.f : 1.f) * c.cull_scale_thresh;
+        const bool far = sqrtf(m[0] * m[0] + m[1] * m[1] + m[2] * m[2]) > c.far_radius;
+        cull = cull || max_exp(sl) > (far ? c.far_factor : 1.f) * c.cull_scale_thresh;
         if (c.cull_screen) cull = cull || max2d > c.cull_screen_size;
     }
     return cull;
@@ -190,12 +191,231 @@ __global__ __launch_bounds__(256) void refine_rows_kernel(int64_t n_out, int64_t
     dst[e] = (zero_new && kind[r] != 0) ? 0.f : src[(int64_t)src_index[r] * w + col];
 }
 
+// ---- the whole scene graph in one pass (include/mtgs_refine_scene.h) -------------------------------------------------------
+// The same decisions, samples and arithmetic as the kernels above (classify, culled, sample_mean, refine_normal3 are shared),
+// per node from a table in device memory: the node's thresholds, options, seed, cull rule and phase.  Gaussian indices are
+// NODE-LOCAL everywhere (the Philox counter, src_index), so a node refines identically alone and inside any scene.
+static_assert(MTGS_REFINE_MAX_COLUMNS == 2 + MAX_SAMPS, "columns: old | MAX_SAMPS children | duplicate");
+
+__device__ __forceinline__ RefineCfg node_cfg(const mtgs_refine_node &d, uint32_t step) {
+    RefineCfg c;
+    c.grad_thresh = d.thresholds[0]; c.size_thresh = d.thresholds[1]; c.split_screen_size = d.thresholds[2];
+    c.cull_alpha_thresh = d.thresholds[3]; c.cull_scale_thresh = d.thresholds[4]; c.cull_screen_size = d.thresholds[5];
+    c.nsamps = d.options[0]; c.use_screen_split = d.options[1]; c.cull_big = d.options[2]; c.cull_screen = d.options[3];
+    c.clone_sample_means = d.options[4];
+    c.seed_lo = (uint32_t)d.seed; c.seed_hi = (uint32_t)(d.seed >> 32); c.step = step;
+    c.far_radius = d.far_radius; c.far_factor = d.far_factor;
+    return c;
+}
+// the node whose workgroups contain `block` (first_block ascending; the search of densify_stats_batch_kernel)
+template <int64_t mtgs_refine_node::*FIRST>
+__device__ __forceinline__ int find_node(const mtgs_refine_node *__restrict__ table, int n_nodes, int64_t block) {
+    int lo = 0, hi = n_nodes - 1;
+    while (lo < hi) {
+        const int mid = (lo + hi + 1) >> 1;
+        if (table[mid].*FIRST <= block) lo = mid; else hi = mid - 1;
+    }
+    return __builtin_amdgcn_readfirstlane(lo);
+}
+
+__global__ __launch_bounds__(256) void refine_scene_classify_kernel(const mtgs_refine_node *__restrict__ table, int n_nodes,
+                                                                   int64_t n_total, int n_columns, uint32_t step,
+                                                                   int32_t *__restrict__ counts /* [n_columns + 1][n_total] */,
+                                                                   uint8_t *__restrict__ flags, uint8_t *__restrict__ parents) {
+    const mtgs_refine_node &d = table[find_node<&mtgs_refine_node::first_block>(table, n_nodes, (int64_t)blockIdx.x)];
+    const int64_t i = ((int64_t)blockIdx.x - d.first_block) * 256 + threadIdx.x;
+    if (i >= d.n) return;
+    const RefineCfg c = node_cfg(d, step);
+    const int64_t g = d.start + i;
+    uint32_t f = 0u;
+    if (d.phase == MTGS_REFINE_CULL_ONLY) {            // cull_gaussians() without a split mask: rows only leave
+        float m[3], sl[3];
+#pragma unroll
+        for (int k = 0; k < 3; ++k) { m[k] = d.means[i * 3 + k]; sl[k] = d.scales[i * 3 + k]; }
+        const float m2 = (c.cull_big && c.cull_screen) ? d.max_2dsize[i] : 0.f;
+        if (!culled(c, m, sl, d.opacities[i], m2)) f = 1u;
+    } else {                                           // refine_classify_kernel, with the node-local index
+        const Node n = classify(c, i, d.means, d.scales, d.quats, d.opacities, d.xys_grad_norm, d.vis_counts, d.max_2dsize);
+        f = n.split ? 0x80u : 0u;
+        if (!n.split && !culled(c, n.m, n.sl, n.opac, d.max_2dsize[i])) f |= 1u;
+        for (int s = 0; s < c.nsamps; ++s) {
+            bool keep = false;
+            if (n.split) {
+                float z[3], cm[3];
+                refine_normal3(c, (uint32_t)i, (uint32_t)s, z);
+                sample_mean(n.m, n.sl, n.q, z, cm);
+                keep = !culled(c, cm, n.sl_cur, n.opac, 0.f);
+            }
+            if (keep) f |= 2u << s;
+        }
+        bool keep_dup = false;
+        if (n.dup) {
+            float dm[3] = {n.m[0], n.m[1], n.m[2]};
+            if (c.clone_sample_means) {
+                float z[3];
+                refine_normal3(c, (uint32_t)i, (uint32_t)c.nsamps, z);
+                sample_mean(n.m, n.sl_cur, n.q, z, dm);
+            }
+            keep_dup = !culled(c, dm, n.sl_cur, n.opac, 0.f);
+        }
+        if (keep_dup) f |= 2u << c.nsamps;
+    }
+    for (int k = 0; k < n_columns; ++k) counts[(int64_t)k * n_total + g] = (int32_t)((f >> k) & 1u);   // (bits above 1 + nsamps are 0)
+    counts[(int64_t)n_columns * n_total + g] = (int32_t)(f >> 7);
+    flags[g] = (uint8_t)f;
+    if (parents) parents[g] = (f & 0x7Eu) != 0u ? 1 : 0;
+}
+
+// incl: INCLUSIVE scans of the count rows over the whole concatenation
+__global__ __launch_bounds__(256) void refine_scene_index_kernel(const mtgs_refine_node *__restrict__ table, int n_nodes,
+                                                                int64_t n_total, const uint8_t *__restrict__ flags,
+                                                                const int64_t *__restrict__ incl, int32_t *__restrict__ src_index,
+                                                                uint8_t *__restrict__ kind) {
+    const mtgs_refine_node &d = table[find_node<&mtgs_refine_node::first_block>(table, n_nodes, (int64_t)blockIdx.x)];
+    const int64_t i = ((int64_t)blockIdx.x - d.first_block) * 256 + threadIdx.x;
+    if (i >= d.n) return;
+    const int64_t g = d.start + i;
+    const uint32_t f = flags[g];
+    const int ncol = 2 + d.options[0];
+    for (int k = 0; k < ncol; ++k) {
+        if ((f >> k) & 1u) {
+            const int64_t local = d.col_base[k] + (incl[(int64_t)k * n_total + g] - 1 - d.scan_base[k]);
+            if (local < 0 || local >= d.n_out) continue;      // (a table that does not belong to these scans: write nothing)
+            src_index[d.out_start + local] = (int32_t)i;
+            kind[d.out_start + local] = (uint8_t)k;
+        }
+    }
+}
+
+__global__ __launch_bounds__(256) void refine_scene_geometry_kernel(const mtgs_refine_node *__restrict__ table, int n_nodes,
+                                                                   uint32_t step, const int32_t *__restrict__ src_index,
+                                                                   const uint8_t *__restrict__ kind, const uint8_t *__restrict__ flags,
+                                                                   float *__restrict__ out_means, float *__restrict__ out_scales) {
+    const mtgs_refine_node &d = table[find_node<&mtgs_refine_node::out_first_block>(table, n_nodes, (int64_t)blockIdx.x)];
+    const int64_t rl = ((int64_t)blockIdx.x - d.out_first_block) * 256 + threadIdx.x;
+    if (rl >= d.n_out) return;
+    const RefineCfg c = node_cfg(d, step);
+    const int64_t r = d.out_start + rl;
+    const int64_t p = src_index[r];
+    if (p < 0 || p >= d.n) return;
+    const int k = kind[r];
+    float m[3], sl[3], sl_cur[3];
+#pragma unroll
+    for (int j = 0; j < 3; ++j) { m[j] = d.means[p * 3 + j]; sl[j] = d.scales[p * 3 + j]; }
+    const bool split = (flags[d.start + p] & 0x80u) != 0;
+#pragma unroll
+    for (int j = 0; j < 3; ++j) sl_cur[j] = split ? logf(expf(sl[j]) / kSplitShrink) : sl[j];
+    float om[3] = {m[0], m[1], m[2]};
+    if (k >= 1 && (k <= c.nsamps || c.clone_sample_means)) {
+        float z[3];
+        refine_normal3(c, (uint32_t)p, (uint32_t)(k - 1), z);
+        const float4 q = reinterpret_cast<const float4 *>(d.quats)[p];
+        if (k <= c.nsamps) sample_mean(m, sl, q, z, om);
+        else sample_mean(m, sl_cur, q, z, om);
+    }
+#pragma unroll
+    for (int j = 0; j < 3; ++j) {
+        out_means[r * 3 + j] = om[j];
+        out_scales[r * 3 + j] = k == 0 ? sl[j] : sl_cur[j];
+    }
+}
+
+// Every remaining tensor of every node: one move per (node, tensor).  A workgroup owns MTGS_REFINE_MOVE_DWORDS consecutive dwords
+// of its move's destination, in chunks of 1024; a lane four dwords of each chunk, shifted so that the four start at a 16-byte
+// boundary: one dwordx4 store per lane and chunk, whatever the row width.  Finding the move (a binary search: dependent loads) and
+// the row and column of the workgroup's first dword (a 64-bit division on uniform operands) are paid once per workgroup, i.e. per
+// 32 KiB moved; a lane's row and column follow from a 32-bit multiply-high and the three dwords after it from an increment.
+// Sources are row gathers: a lane's four dwords come as one dwordx4 load where they lie in one row at a 16-byte boundary (every
+// load of a 4-dword row), otherwise as dword loads that neighbouring lanes coalesce; src_index / kind are read once per row.
+constexpr int MOVE_CHUNK = 1024;
+static_assert(MTGS_REFINE_MOVE_DWORDS % MOVE_CHUNK == 0, "whole chunks");
+__global__ __launch_bounds__(256) void refine_scene_rows_kernel(const mtgs_refine_move *__restrict__ moves, int n_moves,
+                                                               const int32_t *__restrict__ src_index, const uint8_t *__restrict__ kind) {
+    int lo = 0, hi = n_moves - 1;
+    while (lo < hi) {
+        const int mid = (lo + hi + 1) >> 1;
+        if (moves[mid].first_block <= (int64_t)blockIdx.x) lo = mid; else hi = mid - 1;
+    }
+    const mtgs_refine_move &mv = moves[__builtin_amdgcn_readfirstlane(lo)];
+    const uint32_t w = (uint32_t)mv.width;
+    const int op = mv.op;
+    const int64_t total = mv.n_rows * (int64_t)w, n_src = mv.n_src;
+    const float cm = mv.clamp_max;
+    uint32_t *dst = static_cast<uint32_t *>(mv.dst);
+    const uint32_t *src = static_cast<const uint32_t *>(mv.src);
+    const int32_t *idx = src_index + mv.out_start;
+    const uint8_t *kd = kind + mv.out_start;
+    // v = e + pad counts the destination's dwords from the 16-byte boundary at or before dst: a lane's four dwords start at a
+    // multiple of four in v.  Only the move's first workgroup has lanes whose dwords begin before element 0.
+    const int pad = (int)((reinterpret_cast<uintptr_t>(dst) >> 2) & 3u);
+    const int64_t vb = ((int64_t)blockIdx.x - mv.first_block) * MTGS_REFINE_MOVE_DWORDS;
+    const int64_t eb = vb - pad > 0 ? vb - pad : 0;                                // the workgroup's first element
+    const int skip = (int)(eb - (vb - pad));                                       // 0, or pad in the first workgroup
+    const int64_t r0 = eb / (int64_t)w;
+    const uint32_t c0 = (uint32_t)(eb - r0 * (int64_t)w);
+    const uint32_t magic = 0xFFFFFFFFu / w + 1u;                                   // q / w = umulhi(q, magic) while q * w < 2^32: q < 8192 + w, w <= 32768
+    for (int chunk = 0; chunk < MTGS_REFINE_MOVE_DWORDS / MOVE_CHUNK; ++chunk) {
+        const int o0 = chunk * MOVE_CHUNK + 4 * (int)threadIdx.x - skip;           // the lane's first dword, relative to eb (< 0: before element 0)
+        const int first = o0 < 0 ? 0 : o0;
+        if (eb + first >= total) return;
+        const uint32_t q = c0 + (uint32_t)first;
+        const uint32_t dr = w == 1u ? q : __umulhi(q, magic);
+        const int64_t r = r0 + dr;
+        const uint32_t col = q - dr * w;
+        const bool whole = o0 >= 0 && eb + o0 + 4 <= total;
+        uint32_t v[4] = {0u, 0u, 0u, 0u};
+        if (op != MTGS_REFINE_ZERO_ALL) {
+            int64_t rr = r, p = idx[r];
+            uint32_t cc = col;
+            bool zero = (op == MTGS_REFINE_ZERO_NEW && kd[r] != 0) || p < 0 || p >= n_src;   // (an index that is no row: zeros, nothing followed)
+            const uint32_t *sp = src + p * w + col;
+            if (whole && col + 4u <= w && (zero || (reinterpret_cast<uintptr_t>(sp) & 15u) == 0)) {   // four dwords of one row, aligned
+                if (!zero) {
+                    const uint4 t = *reinterpret_cast<const uint4 *>(sp);
+                    v[0] = t.x; v[1] = t.y; v[2] = t.z; v[3] = t.w;
+                }
+            } else {
+#pragma unroll
+                for (int j = 0; j < 4; ++j) {
+                    const int o = o0 + j;
+                    if (o >= 0 && eb + o < total) {
+                        if (cc == w) {                                             // the next row
+                            cc = 0; ++rr;
+                            p = idx[rr];
+                            zero = (op == MTGS_REFINE_ZERO_NEW && kd[rr] != 0) || p < 0 || p >= n_src;
+                        }
+                        v[j] = zero ? 0u : src[p * w + cc];
+                        ++cc;
+                    }
+                }
+            }
+            if (op == MTGS_REFINE_CLAMP_MAX) {
+#pragma unroll
+                for (int j = 0; j < 4; ++j) {
+                    const float x = __uint_as_float(v[j]);
+                    v[j] = __float_as_uint(x > cm ? cm : x);                       // (torch.clamp(max=): a NaN stays)
+                }
+            }
+        }
+        if (whole) {
+            *reinterpret_cast<uint4 *>(dst + eb + o0) = uint4{v[0], v[1], v[2], v[3]};
+        } else {
+#pragma unroll
+            for (int j = 0; j < 4; ++j) {
+                const int o = o0 + j;
+                if (o >= 0 && eb + o < total) dst[eb + o] = v[j];
+            }
+        }
+    }
+}
+
 RefineCfg make_cfg(const float *th, const int *opt, uint64_t seed, int64_t step) {
     RefineCfg c;
     c.grad_thresh = th[0]; c.size_thresh = th[1]; c.split_screen_size = th[2]; c.cull_alpha_thresh = th[3];
     c.cull_scale_thresh = th[4]; c.cull_screen_size = th[5];
     c.nsamps = opt[0]; c.use_screen_split = opt[1]; c.cull_big = opt[2]; c.cull_screen = opt[3]; c.clone_sample_means = opt[4];
     c.seed_lo = (uint32_t)seed; c.seed_hi = (uint32_t)(seed >> 32); c.step = (uint32_t)step;
+    c.far_radius = 100.f; c.far_factor = 40.f;      // VanillaGaussianSplattingModel.cull_gaussians (:599-600)
     return c;
 }
 
@@ -242,5 +462,85 @@ extern "C" int mtgs_refine_rows(int64_t n_out, int64_t width, const float *src, 
     refine_rows_kernel<<<(unsigned)ceil_div64(n_out * width, 256), 256, 0, (hipStream_t)stream>>>(n_out, width, src, src_index, kind,
                                                                                                zero_new, dst);
     MTGS_CHECK_LAUNCH("mtgs_refine_rows");
+    return MTGS_OK;
+}
+
+// ---- the scene-wide entry points (include/mtgs_refine_scene.h) ---------------------------------------------------------------
+extern "C" int mtgs_refine_scene_table_bytes(size_t *node_bytes, size_t *move_bytes) {
+    MTGS_REQUIRE(node_bytes, MTGS_EINVAL, "mtgs_refine_scene_table_bytes: null pointer: node_bytes");
+    MTGS_REQUIRE(move_bytes, MTGS_EINVAL, "mtgs_refine_scene_table_bytes: null pointer: move_bytes");
+    *node_bytes = sizeof(mtgs_refine_node);
+    *move_bytes = sizeof(mtgs_refine_move);
+    return MTGS_OK;
+}
+
+#define REFINE_SCENE_PTR(fn, p) \
+    MTGS_REQUIRE(p, MTGS_EINVAL, fn ": null pointer: " #p)
+
+extern "C" int mtgs_refine_scene_classify(int n_nodes, const mtgs_refine_node *table, int64_t total_blocks, int64_t n_total,
+                                          int n_columns, int64_t step, int32_t *counts, uint8_t *flags, uint8_t *parents,
+                                          void *stream) {
+    MTGS_REQUIRE(n_nodes >= 0, MTGS_EINVAL, "mtgs_refine_scene_classify: n_nodes < 0 (%d)", n_nodes);
+    MTGS_REQUIRE(n_total >= 0 && n_total < ((int64_t)1 << 31), MTGS_EINVAL,
+                 "mtgs_refine_scene_classify: n_total outside [0, 2^31) (%lld)", (long long)n_total);
+    MTGS_REQUIRE(n_columns >= 3 && n_columns <= MTGS_REFINE_MAX_COLUMNS, MTGS_EUNSUPPORTED,
+                 "mtgs_refine_scene_classify: n_columns outside [3, %d] (%d)", MTGS_REFINE_MAX_COLUMNS, n_columns);
+    MTGS_REQUIRE(total_blocks >= 0 && total_blocks <= n_total, MTGS_EINVAL,
+                 "mtgs_refine_scene_classify: total_blocks outside [0, n_total] (%lld)", (long long)total_blocks);
+    if (n_nodes == 0 || n_total == 0 || total_blocks == 0) return MTGS_OK;
+    REFINE_SCENE_PTR("mtgs_refine_scene_classify", table);
+    REFINE_SCENE_PTR("mtgs_refine_scene_classify", counts);
+    REFINE_SCENE_PTR("mtgs_refine_scene_classify", flags);
+    MTGS_REQUIRE((reinterpret_cast<uintptr_t>(table) & 7) == 0, MTGS_EINVAL, "mtgs_refine_scene_classify: table must be 8-byte aligned");
+    refine_scene_classify_kernel<<<(unsigned)total_blocks, 256, 0, (hipStream_t)stream>>>(table, n_nodes, n_total, n_columns,
+                                                                                          (uint32_t)step, counts, flags, parents);
+    MTGS_CHECK_LAUNCH("mtgs_refine_scene_classify");
+    return MTGS_OK;
+}
+
+extern "C" int mtgs_refine_scene_apply(int n_nodes, const mtgs_refine_node *table, int64_t total_blocks, int64_t out_blocks,
+                                       int64_t n_total, int64_t n_out_total, int n_columns, int64_t step, const uint8_t *flags,
+                                       const int64_t *incl, int32_t *src_index, uint8_t *kind, float *out_means, float *out_scales,
+                                       void *stream) {
+    MTGS_REQUIRE(n_nodes >= 0, MTGS_EINVAL, "mtgs_refine_scene_apply: n_nodes < 0 (%d)", n_nodes);
+    MTGS_REQUIRE(n_total >= 0 && n_total < ((int64_t)1 << 31), MTGS_EINVAL,
+                 "mtgs_refine_scene_apply: n_total outside [0, 2^31) (%lld)", (long long)n_total);
+    MTGS_REQUIRE(n_out_total >= 0 && n_out_total < ((int64_t)1 << 31), MTGS_EINVAL,
+                 "mtgs_refine_scene_apply: n_out_total outside [0, 2^31) (%lld)", (long long)n_out_total);
+    MTGS_REQUIRE(n_columns >= 3 && n_columns <= MTGS_REFINE_MAX_COLUMNS, MTGS_EUNSUPPORTED,
+                 "mtgs_refine_scene_apply: n_columns outside [3, %d] (%d)", MTGS_REFINE_MAX_COLUMNS, n_columns);
+    MTGS_REQUIRE(total_blocks >= 0 && total_blocks <= n_total, MTGS_EINVAL,
+                 "mtgs_refine_scene_apply: total_blocks outside [0, n_total] (%lld)", (long long)total_blocks);
+    MTGS_REQUIRE(out_blocks >= 0 && out_blocks <= n_out_total, MTGS_EINVAL,
+                 "mtgs_refine_scene_apply: out_blocks outside [0, n_out_total] (%lld)", (long long)out_blocks);
+    if (n_nodes == 0 || n_total == 0 || n_out_total == 0 || total_blocks == 0 || out_blocks == 0) return MTGS_OK;
+    REFINE_SCENE_PTR("mtgs_refine_scene_apply", table);
+    REFINE_SCENE_PTR("mtgs_refine_scene_apply", flags);
+    REFINE_SCENE_PTR("mtgs_refine_scene_apply", incl);
+    REFINE_SCENE_PTR("mtgs_refine_scene_apply", src_index);
+    REFINE_SCENE_PTR("mtgs_refine_scene_apply", kind);
+    REFINE_SCENE_PTR("mtgs_refine_scene_apply", out_means);
+    REFINE_SCENE_PTR("mtgs_refine_scene_apply", out_scales);
+    MTGS_REQUIRE((reinterpret_cast<uintptr_t>(table) & 7) == 0, MTGS_EINVAL, "mtgs_refine_scene_apply: table must be 8-byte aligned");
+    hipStream_t st = (hipStream_t)stream;
+    refine_scene_index_kernel<<<(unsigned)total_blocks, 256, 0, st>>>(table, n_nodes, n_total, flags, incl, src_index, kind);
+    refine_scene_geometry_kernel<<<(unsigned)out_blocks, 256, 0, st>>>(table, n_nodes, (uint32_t)step, src_index, kind, flags,
+                                                                        out_means, out_scales);
+    MTGS_CHECK_LAUNCH("mtgs_refine_scene_apply");
+    return MTGS_OK;
+}
+
+extern "C" int mtgs_refine_scene_rows(int n_moves, const mtgs_refine_move *moves, int64_t total_blocks, const int32_t *src_index,
+                                      const uint8_t *kind, void *stream) {
+    MTGS_REQUIRE(n_moves >= 0, MTGS_EINVAL, "mtgs_refine_scene_rows: n_moves < 0 (%d)", n_moves);
+    MTGS_REQUIRE(total_blocks >= 0 && total_blocks < ((int64_t)1 << 31), MTGS_EINVAL,
+                 "mtgs_refine_scene_rows: total_blocks outside [0, 2^31) (%lld)", (long long)total_blocks);
+    if (n_moves == 0 || total_blocks == 0) return MTGS_OK;
+    REFINE_SCENE_PTR("mtgs_refine_scene_rows", moves);
+    REFINE_SCENE_PTR("mtgs_refine_scene_rows", src_index);
+    REFINE_SCENE_PTR("mtgs_refine_scene_rows", kind);
+    MTGS_REQUIRE((reinterpret_cast<uintptr_t>(moves) & 7) == 0, MTGS_EINVAL, "mtgs_refine_scene_rows: moves must be 8-byte aligned");
+    refine_scene_rows_kernel<<<(unsigned)total_blocks, 256, 0, (hipStream_t)stream>>>(moves, n_moves, src_index, kind);
+    MTGS_CHECK_LAUNCH("mtgs_refine_scene_rows");
     return MTGS_OK;
 }

@@ -141,6 +141,7 @@ class RefineConfig:
     stop_screen_size_at: int = 15000
     cull_screen_size: float = 150.0
     split_screen_size: float = 100.0
+    densify_from_iter: int = 500       # refine_scene's gate (step <= densify_from_iter: untouched); refine_gaussians ignores it
 
 
 @torch.no_grad()
@@ -237,3 +238,257 @@ def reset_opacities(opacities: Tensor, cfg: RefineConfig, moments: Optional[Tupl
     if moments is not None:
         moments[0].zero_()
         moments[1].zero_()
+
+
+# ------------------------------------------------------------------------------------- refinement of a whole scene graph
+from typing import List
+
+from ._abi import header_abi as _header_abi
+
+_SCENE_ABI = _header_abi("mtgs_refine_scene.h")          # include/mtgs_refine_scene.h
+_REFINE_NODE = _SCENE_ABI.structs["mtgs_refine_node"]
+_REFINE_MOVE = _SCENE_ABI.structs["mtgs_refine_move"]
+_DENSIFY, _CULL_ONLY = _SCENE_ABI.constants["MTGS_REFINE_DENSIFY"], _SCENE_ABI.constants["MTGS_REFINE_CULL_ONLY"]
+_COPY, _ZERO_NEW, _CLAMP_MAX, _ZERO_ALL = (_SCENE_ABI.constants["MTGS_REFINE_" + k] for k in ("COPY", "ZERO_NEW", "CLAMP_MAX", "ZERO_ALL"))
+_MOVE_DWORDS = _SCENE_ABI.constants["MTGS_REFINE_MOVE_DWORDS"]     # dwords of a move one workgroup of mtgs_refine_scene_rows works on
+_GEOMETRY = ("means", "scales", "quats", "opacities")
+
+
+@dataclass
+class NodeRefine:
+    """One node of the scene graph as refine_scene sees it.  params / stats / cfg / seed / moments / extras: the arguments of
+    refine_gaussians (MTGS overlays the control config per node, mtgs_scene_graph.py:194-205, hence a cfg per node).
+    stats None: the node never collected statistics (rigid_node.py:356-366, deformable_node.py:288-298).
+    cull_rule = (far radius, far factor): beyond |mean| > radius the world-size limit is factor x cull_scale_thresh.
+    (100, 40) is VanillaGaussianSplattingModel.cull_gaussians (:599-600); the sky node takes
+    (skybox_radius / 10, skybox_scale_factor) (skybox_gaussian_splatting.py:147-148).  frozen: the node's `frozen` flag (:478)."""
+    params: Dict[str, Tensor]
+    stats: Optional[Tuple[Tensor, Tensor, Tensor]]
+    cfg: RefineConfig
+    seed: int
+    moments: Optional[Dict[str, Tuple[Tensor, Tensor]]] = None
+    extras: Optional[Dict[str, Tensor]] = None
+    cull_rule: Tuple[float, float] = (100.0, 40.0)
+    frozen: bool = False
+
+
+def refine_phase(node: NodeRefine, step: int) -> int:
+    """What refinement_after does with this node at `step` (vanilla_gaussian_splatting.py:476-550): 0 untouched,
+    MTGS_REFINE_DENSIFY or MTGS_REFINE_CULL_ONLY.  No tensor is read."""
+    cfg = node.cfg
+    if node.frozen or step <= cfg.densify_from_iter or node.params["means"].shape[0] == 0:       # :478-484
+        return 0
+    if step < cfg.stop_split_at:                                                                  # :486
+        return 0 if node.stats is None else _DENSIFY       # (the rigid / deformable skip; a vanilla node asserts at :491)
+    return _CULL_ONLY if cfg.continue_cull_post_densification else 0                              # :546-550
+
+
+def _c(t: Tensor) -> Tensor:
+    return t if t.is_contiguous() else t.contiguous()
+
+
+@torch.no_grad()
+def refine_scene(nodes: Sequence[NodeRefine], step: int, before_rows=None) -> List[Optional[Tuple[dict, Optional[dict], dict]]]:
+    """refinement_after (vanilla_gaussian_splatting.py:476-577) for EVERY node of a scene graph in one pass: one classify launch,
+    one prefix sum, ONE blocking host read (the per-node, per-column survivor totals, which fix the new sizes), one index and one
+    geometry launch and one table-driven launch that moves every remaining tensor of every node -- whatever the number of nodes.
+
+    Per node, as the reference gates it:
+      untouched (result None, no tensor read or written): frozen, step <= cfg.densify_from_iter, N == 0; in the densify phase
+        with stats None -- the "never seen, skip" rule of the rigid and deformable nodes; a VANILLA node in that state asserts in
+        the reference (:491), here it is skipped like the others; and past stop_split_at without
+        continue_cull_post_densification.
+      densify (step < stop_split_at): exactly refine_gaussians(params, stats, cfg, step, seed, ...) -- the samples are keyed by
+        (node seed, step, node-local Gaussian index, slot), so the result is bit-identical to that call whatever the node's
+        neighbours are -- with the cull rule node.cull_rule in place of the constants 100 / 40, and, when
+        step % (reset_alpha_every * refine_every) == refine_every, followed in the same pass by reset_opacities (:555-573):
+        the new opacities clamped at logit(2 cull_alpha_thresh), their moments zero.
+      cull-only (step >= stop_split_at and continue_cull_post_densification): cull_gaussians() alone (:546-547); rows only leave,
+        the moments follow, stats may be None unless the screen-size rule is still on (step < stop_screen_size_at), which reads
+        max_2Dsize: ValueError, as the reference asserts (:607).
+
+    Returns one entry per node: None, or (new_params, new_moments | None, info) with refine_gaussians' info keys (n_split is a
+    host int here: it comes with the one host read).  The new tensors are VIEWS of one buffer per tensor name (and row shape):
+    a hundred nodes do not cost a hundred allocations per tensor.  before_rows(masks): called once, after all decisions and
+    before any row moves, masks[i] = bool [N_i] of the Gaussians of node i that get children or a duplicate (None for an untouched
+    node); as in refine_gaussians the four geometry tensors must be current before the call.  extras move like parameters.
+    Isotropic nodes (scales[N, 1], no quats) are not supported: NotImplementedError."""
+    from ._lib import call, ptr, stream_of
+    from .nodes import upload_table
+    results: List[Optional[tuple]] = [None] * len(nodes)
+    act = []                                               # (index into nodes, phase)
+    for j, nd in enumerate(nodes):                         # what is not supported, before anything else
+        scales = nd.params["scales"]
+        if "quats" not in nd.params or scales.dim() != 2 or scales.shape[1] != 3:
+            raise NotImplementedError(f"refine_scene: node {j} is isotropic (scales {tuple(scales.shape)}, "
+                                      f"{'no ' if 'quats' not in nd.params else ''}quats): only scale_dim == 3 nodes are supported")
+    for j, nd in enumerate(nodes):
+        p = nd.params
+        means, scales = p["means"], p["scales"]
+        N = means.shape[0]
+        require_gpu(*p.values(), *(nd.stats or ()), *(nd.extras or {}).values(), *(t for ab in (nd.moments or {}).values() for t in ab))
+        if means.shape != (N, 3) or scales.shape != (N, 3) or p["quats"].shape != (N, 4) or p["opacities"].numel() != N:
+            raise ValueError(f"refine_scene: node {j}: means[N,3], scales[N,3], quats[N,4], opacities[N(,1)] expected")
+        for k, t in p.items():
+            if t.dtype != torch.float32 or t.shape[0] != N:
+                raise ValueError(f"refine_scene: node {j}: parameter {k!r} must be float32 with one row per Gaussian")
+        for k, (a, b) in (nd.moments or {}).items():
+            if k not in p or a.shape != p[k].shape or b.shape != p[k].shape or a.dtype != torch.float32 or b.dtype != torch.float32:
+                raise ValueError(f"refine_scene: node {j}: moments of {k!r} must be two float32 tensors of the parameter's shape")
+        for k, t in (nd.extras or {}).items():
+            if t.shape[0] != N or t.element_size() != 4:
+                raise ValueError(f"refine_scene: node {j}: extra {k!r} must be an [N, ...] tensor of a 4-byte dtype")
+        if not 1 <= int(nd.cfg.n_split_samples) <= 4:
+            raise ValueError(f"refine_scene: node {j}: n_split_samples={nd.cfg.n_split_samples} (1..4)")
+        ph = refine_phase(nd, step)
+        if ph:
+            act.append((j, ph))
+    if not act:
+        return results
+    A = len(act)
+    dev = nodes[act[0][0]].params["means"].device
+    st = stream_of(nodes[act[0][0]].params["means"])
+    nb, mb = _C.c_size_t(0), _C.c_size_t(0)
+    call("mtgs_refine_scene_table_bytes", _C.byref(nb), _C.byref(mb))
+    if (nb.value, mb.value) != (_REFINE_NODE.itemsize, _REFINE_MOVE.itemsize):
+        raise RuntimeError("mtgs_refine_node / mtgs_refine_move layout mismatch between libmtgs_rast.so and mtgs_amd.densify")
+
+    # ---- the node table: sizes, pointers, thresholds, options, rule, phase ---------------------------------------------------
+    tab = np.zeros(A, dtype=_REFINE_NODE)
+    keep_alive = []                                        # converted inputs (non-contiguous / non-float32 statistics): rare
+    geo = {k: [] for k in _GEOMETRY}
+    stat_ptrs = ([], [], [])
+    n, resets = np.zeros(A, dtype=np.int64), [False] * A
+    for i, (j, ph) in enumerate(act):
+        nd, cfg = nodes[j], nodes[j].cfg
+        n[i] = nd.params["means"].shape[0]
+        for k in _GEOMETRY:
+            t = _c(nd.params[k])
+            keep_alive.append(t)
+            geo[k].append(t.data_ptr())
+        cull_big = step > cfg.refine_every * cfg.reset_alpha_every
+        opt = (int(cfg.n_split_samples), int(step < cfg.stop_screen_size_at), int(cull_big),
+               int(cull_big and step < cfg.stop_screen_size_at), int(cfg.clone_sample_means))
+        if nd.stats is None:
+            if opt[3]:
+                raise ValueError(f"refine_scene: node {j}: the screen-size cull rule is on at step {step} "
+                                 f"(< stop_screen_size_at = {cfg.stop_screen_size_at}) and reads max_2Dsize: stats must not be None")
+            for q in stat_ptrs:
+                q.append(0)
+        else:
+            for q, t in zip(stat_ptrs, nd.stats):
+                if t.numel() != n[i]:
+                    raise ValueError(f"refine_scene: node {j}: statistics must have one element per Gaussian")
+                if t.dtype != torch.float32 or not t.is_contiguous():
+                    t = t.to(torch.float32).contiguous()
+                    keep_alive.append(t)
+                q.append(t.data_ptr())
+        tab["thresholds"][i] = (cfg.densify_grad_thresh, cfg.densify_size_thresh, cfg.split_screen_size, cfg.cull_alpha_thresh,
+                                cfg.cull_scale_thresh, cfg.cull_screen_size)
+        tab["options"][i] = opt
+        tab["far_radius"][i], tab["far_factor"][i] = nd.cull_rule
+        tab["seed"][i] = nd.seed & (2 ** 64 - 1)
+        tab["phase"][i] = ph
+        resets[i] = ph == _DENSIFY and step % (cfg.reset_alpha_every * cfg.refine_every) == cfg.refine_every     # :555
+    nblk = (n + 255) // 256
+    n_total, total_blocks = int(n.sum()), int(nblk.sum())
+    if n_total >= 2 ** 31:
+        raise ValueError(f"refine_scene: {n_total} Gaussians in the scene (limit 2^31 - 1)")
+    tab["n"], tab["start"], tab["first_block"] = n, np.cumsum(n) - n, np.cumsum(nblk) - nblk
+    for k in _GEOMETRY:
+        tab[k] = geo[k]
+    for k, q in zip(("xys_grad_norm", "vis_counts", "max_2dsize"), stat_ptrs):
+        tab[k] = q
+    ncol = 2 + int(tab["options"][:, 0].max())
+
+    # ---- decisions, prefix sums, the one host read ---------------------------------------------------------------------------
+    counts = torch.empty((ncol + 1, n_total), dtype=torch.int32, device=dev)
+    flags = torch.empty(n_total, dtype=torch.uint8, device=dev)
+    parents = torch.empty(n_total, dtype=torch.uint8, device=dev) if before_rows is not None else None
+    ends = upload_table(np.cumsum(n) - 1, dev).view(torch.int64)
+    call("mtgs_refine_scene_classify", A, ptr(upload_table(tab, dev)), total_blocks, n_total, ncol, int(step), ptr(counts), ptr(flags),
+         ptr(parents), st)
+    incl = torch.cumsum(counts, dim=1, dtype=torch.int64)
+    bound = incl.index_select(1, ends).cpu().numpy()       # [ncol + 1, A]: THE host synchronisation
+    before = np.concatenate([np.zeros((ncol + 1, 1), dtype=np.int64), bound[:, :-1]], axis=1)
+    tot = bound - before                                   # survivors per column and node; last row: split parents
+    n_out = tot[:ncol].sum(axis=0)
+    oblk = (n_out + 255) // 256
+    out_start = np.cumsum(n_out) - n_out
+    n_out_total, out_blocks = int(n_out.sum()), int(oblk.sum())
+    if n_out_total >= 2 ** 31:
+        raise ValueError(f"refine_scene: {n_out_total} Gaussians after the refinement (limit 2^31 - 1)")
+    tab["n_out"], tab["out_start"], tab["out_first_block"] = n_out, out_start, np.cumsum(oblk) - oblk
+    tab["scan_base"][:, :ncol] = before[:ncol].T
+    tab["col_base"][:, :ncol] = (np.cumsum(tot[:ncol], axis=0) - tot[:ncol]).T
+    src_index = torch.empty(n_out_total, dtype=torch.int32, device=dev)
+    kind = torch.empty(n_out_total, dtype=torch.uint8, device=dev)
+    out_means = torch.empty((n_out_total, 3), dtype=torch.float32, device=dev)
+    out_scales = torch.empty((n_out_total, 3), dtype=torch.float32, device=dev)
+    call("mtgs_refine_scene_apply", A, ptr(upload_table(tab, dev)), total_blocks, out_blocks, n_total, n_out_total, ncol, int(step),
+         ptr(flags), ptr(incl), ptr(src_index), ptr(kind), ptr(out_means), ptr(out_scales), st)
+
+    if before_rows is not None:
+        masks: List[Optional[Tensor]] = [None] * len(nodes)
+        for (j, _), m in zip(act, parents.view(torch.bool).split(n.tolist())):
+            masks[j] = m
+        before_rows(masks)
+
+    # ---- every remaining tensor: one buffer per (tensor, row shape), one move per (node, tensor) ----------------------------------
+    rows = n_out.tolist()
+    groups: Dict[tuple, list] = {}                         # (what, name, row shape, dtype) -> [(active node, source, op, clamp)]
+    for i, (j, ph) in enumerate(act):
+        nd, cfg = nodes[j], nodes[j].cfg
+        v = 2.0 * cfg.cull_alpha_thresh
+        clamp = float(np.log(v / (1.0 - v)))
+        for k, t in nd.params.items():
+            if k in ("means", "scales"):
+                continue
+            op = _CLAMP_MAX if (k == "opacities" and resets[i]) else _COPY
+            groups.setdefault(("p", k, tuple(t.shape[1:]), t.dtype), []).append((i, t, op, clamp))
+        for k, ab in (nd.moments or {}).items():
+            op = _ZERO_ALL if (k == "opacities" and resets[i]) else _ZERO_NEW
+            for h, t in enumerate(ab):
+                groups.setdefault(("m%d" % h, k, tuple(t.shape[1:]), t.dtype), []).append((i, t, op, 0.0))
+        for k, t in (nd.extras or {}).items():
+            groups.setdefault(("x", k, tuple(t.shape[1:]), t.dtype), []).append((i, t, _COPY, 0.0))
+    moved: Dict[tuple, Tensor] = {}                        # (what, name, active node) -> the node's view
+    mv_cols = ([], [], [], [], [], [], [], [])             # n_rows, out_start, n_src, src, dst, width, op, clamp_max
+    for (what, name, shape, dtype), members in groups.items():
+        w = int(np.prod(shape, dtype=np.int64)) if shape else 1
+        if not 1 <= w <= 32768:
+            raise ValueError(f"refine_scene: {name!r}: rows of {w} elements (1..32768)")
+        sizes = [rows[i] for i, *_ in members]
+        buf = torch.empty((sum(sizes),) + shape, dtype=dtype, device=dev)
+        base, off = buf.data_ptr(), 0
+        for (i, t, op, clamp), view, r in zip(members, buf.split(sizes), sizes):
+            moved[(what, name, i)] = view
+            if r:
+                t = _c(t)
+                keep_alive.append(t)
+                for col, val in zip(mv_cols, (r, int(out_start[i]), int(n[i]), t.data_ptr(), base + off * w * 4, w, op, clamp)):
+                    col.append(val)
+            off += r
+    M = len(mv_cols[0])
+    if M:
+        mv = np.zeros(M, dtype=_REFINE_MOVE)
+        for key, col in zip(("n_rows", "out_start", "n_src", "src", "dst", "width", "op", "clamp_max"), mv_cols):
+            mv[key] = col
+        blocks = (mv["n_rows"] * mv["width"] + 3 + _MOVE_DWORDS - 1) // _MOVE_DWORDS
+        mv["first_block"] = np.cumsum(blocks) - blocks
+        call("mtgs_refine_scene_rows", M, ptr(upload_table(mv, dev)), int(blocks.sum()), ptr(src_index), ptr(kind), st)
+
+    # ---- the nodes' results: views ------------------------------------------------------------------------------------------------
+    means_v, scales_v = out_means.split(rows), out_scales.split(rows)
+    src_v, kind_v = src_index.split(rows), kind.split(rows)
+    for i, (j, ph) in enumerate(act):
+        nd = nodes[j]
+        S = int(nd.cfg.n_split_samples)
+        new = {k: (means_v[i] if k == "means" else scales_v[i] if k == "scales" else moved[("p", k, i)]) for k in nd.params}
+        new_m = None if nd.moments is None else {k: (moved[("m0", k, i)], moved[("m1", k, i)]) for k in nd.moments}
+        t = tot[:, i].tolist()
+        info = {"n_before": int(n[i]), "n_after": rows[i], "n_old_kept": t[0], "n_children": sum(t[1:1 + S]), "n_dups": t[1 + S],
+                "n_split": t[ncol], "src_index": src_v[i], "kind": kind_v[i],
+                "extras": {k: moved[("x", k, i)] for k in (nd.extras or {})}}
+        results[j] = (new, new_m, info)
+    return results

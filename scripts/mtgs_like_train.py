@@ -456,7 +456,7 @@ def iteration_nograd(P, cam, gt, mask, stats, win, W, H, shipped):
     return 0.8 * masked_l1(gt, rgb, mask) + 0.2 * (1 - masked_ssim(gt, rgb, mask))
 
 
-def refine_device(P, stats, opt_state_of, step, seed, growth=0.02, cfg=None, lazy_opt=None):
+def refine_device(P, stats, opt_state_of, step, seed, growth=0.02, cfg=None, lazy_opt=None, scene=False):
     """Densification of every static node with mtgs_amd.densify.refine_gaussians (csrc/refine.hip): the reference's rules
     (vanilla_gaussian_splatting.py:476-699) on the device, Adam moments following their rows, samples from a generator keyed
     by (seed, step, Gaussian index) -- identical on every rank of a data-parallel run.  The gradient threshold is set per
@@ -470,14 +470,21 @@ def refine_device(P, stats, opt_state_of, step, seed, growth=0.02, cfg=None, laz
     like the moments do (refine_gaussians(extras=...)), and only the Gaussians that get children or a duplicate, whose current
     values the new rows copy, are caught up first (before_rows -> FusedAdam.catch_up_rows).  swap[...] then carries
     (last, hist) for the next optimizer's set_row_lazy.
+    scene (--refine-scene): EVERY node, the rigid object nodes included, in one pass of mtgs_amd.densify.refine_scene -- one host
+    synchronisation and a fixed number of launches whatever the number of nodes; the per-frame pose parameters of an object node
+    (instance_quats / instance_trans) are no per-Gaussian tensors and stay as they are.
     Returns (added, culled, {old parameter id: (old, new parameter, new moments | None, (last, hist) | None)})."""
-    from mtgs_amd.densify import RefineConfig, refine_gaussians, reset_opacities
+    from dataclasses import replace
+    from mtgs_amd.densify import NodeRefine, RefineConfig, refine_gaussians, refine_scene, reset_opacities
     added = culled = 0
     swap = {}
     fixed = cfg
+    jobs = []
     for (name, p), st in zip(list(P.items()), stats):
         if "instance_quats" in p:
-            continue
+            if not scene:
+                continue
+            p = {k: v for k, v in p.items() if not k.startswith("instance_")}       # (the per-Gaussian tensors of a rigid node)
         if fixed is None:
             avg = st[0] / st[1]
             thr = float(torch.quantile(avg[:: max(1, avg.numel() // 1_000_000)], 1.0 - growth))
@@ -497,18 +504,42 @@ def refine_device(P, stats, opt_state_of, step, seed, growth=0.02, cfg=None, laz
                 T_k = stt[0].numel() // max(n_old, 1)
                 items += [(p[k], m, (t_ if T_k > 1 else None)) for t_ in range(T_k)]
             lazy_opt.catch_up_rows(items)
-        new, new_m, info = refine_gaussians({k: v.detach() for k, v in p.items()}, tuple(st), cfg, step, seed,
-                                            moments=moments or None, extras=extras or None,
-                                            before_rows=before_rows if lazy else None)
-        if fixed is not None and step % (cfg.reset_alpha_every * cfg.refine_every) == cfg.refine_every:
-            reset_opacities(new["opacities"], cfg, new_m.get("opacities") if new_m else None)
+        jobs.append((name, p, st, cfg, moments, extras, lazy, before_rows))
+
+    if scene:
+        # the caller gates the step (densify_from); the reset follows the reference's schedule only with fixed thresholds, as below
+        nodes = [NodeRefine({k: v.detach() for k, v in p.items()}, tuple(st),
+                            replace(cfg, densify_from_iter=0, stop_split_at=max(cfg.stop_split_at, step + 1),
+                                    reset_alpha_every=cfg.reset_alpha_every if fixed is not None else 10 ** 9),
+                            seed, moments=moments or None, extras=extras or None)
+                 for _, p, st, cfg, moments, extras, _, _ in jobs]
+        hooks = [(j[7] if j[6] else None) for j in jobs]
+
+        def before_all(masks):
+            for hook, m in zip(hooks, masks):
+                if hook is not None and m is not None:
+                    hook(m)
+        results = refine_scene(nodes, step, before_rows=before_all if any(hooks) else None)
+    else:
+        results = []
+        for name, p, st, cfg, moments, extras, lazy, before_rows in jobs:
+            new, new_m, info = refine_gaussians({k: v.detach() for k, v in p.items()}, tuple(st), cfg, step, seed,
+                                                moments=moments or None, extras=extras or None,
+                                                before_rows=before_rows if lazy else None)
+            if fixed is not None and step % (cfg.reset_alpha_every * cfg.refine_every) == cfg.refine_every:
+                reset_opacities(new["opacities"], cfg, new_m.get("opacities") if new_m else None)
+            results.append((new, new_m, info))
+    for (name, p, st, cfg, moments, extras, lazy, _), res in zip(jobs, results):
+        if res is None:                              # (an empty node)
+            continue
+        new, new_m, info = res
         n_new = info["n_after"]
         for k, v in p.items():
             q = new[k].requires_grad_(True)
             carry = (info["extras"]["last:" + k].reshape(-1).contiguous(), lazy[k][1]) if k in lazy else None
             swap[id(v)] = (v, q, new_m.get(k) if new_m else None, carry)
             new[k] = q
-        P[name] = new
+        P[name] = dict(new, **{k: v for k, v in P[name].items() if k.startswith("instance_")})
         added += info["n_children"] + info["n_dups"]
         culled += info["n_before"] - info["n_old_kept"]
         dev = new["means"].device
@@ -527,6 +558,7 @@ LR_SETS = {
                   "scales": 5e-3, "quats": 1e-3, "instance_quats": 1e-3, "instance_trans": 8e-4, "exposure": 1e-3},
 }
 LR = {"set": "harness"}
+REFINE_SCENE = {"on": False}      # --refine-scene: refine_device through mtgs_amd.densify.refine_scene, object nodes included
 
 
 def make_optimizer(kind, P, shipped=None, capturable=False):
@@ -787,7 +819,7 @@ def train_loop(P, cams, targets, mask, win, W, H, steps, refine_every, shipped=N
             state = {id(q): opt.state.get(q) for q in params}
             tick("flush")
             added, culled, swap = refine_device(P, stats, lambda q: state.get(id(q)), i + 1, seed, cfg=refine_cfg,
-                                                lazy_opt=opt if (ROWLAZY["on"] or DPROWS["on"]) else None)
+                                                lazy_opt=opt if (ROWLAZY["on"] or DPROWS["on"]) else None, scene=REFINE_SCENE["on"])
             tick("refine_device")
             old_opt, opt = opt, make_opt()
             carry = {}
@@ -850,6 +882,8 @@ def main():
                     "exposure model, inverse-depth and normal losses")
     ap.add_argument("--steps", type=int, default=0)
     ap.add_argument("--refine-every", type=int, default=0, help="with --steps: densify (duplicate / split / cull) every so many steps")
+    ap.add_argument("--refine-scene", action="store_true", help="with --refine-every: refine EVERY node, the object nodes included, in one "
+                    "pass of mtgs_amd.densify.refine_scene instead of one refine_gaussians call per static node")
     ap.add_argument("--reps", type=int, default=10)
     ap.add_argument("--only", choices=["both", "fused", "chain"], default="both", help="profiling aid: time one variant only")
     ap.add_argument("--dp", action="store_true", help="with --steps: view-parallel data parallelism under torch.distributed.run "
@@ -910,6 +944,7 @@ def main():
                     "with --converge; 0 otherwise)")
     ap.add_argument("--trace-refinements", action="store_true", help="print the loss around every refinement")
     args = ap.parse_args()
+    REFINE_SCENE["on"] = args.refine_scene
     if args.visfirst and (args.accumulate > 1 or args.dp):
         raise SystemExit("--visfirst hands the gradients to the optimizer as rows of ONE frame: not with --accumulate > 1 or --dp "
                          "(the sparse exchange has its own row path)")

@@ -10,7 +10,7 @@ extern "C" {
 
 /* ---- rendering inside an oriented crop box (mtgs_amd/csrc/crop.hip): MTGSSceneModel.get_gaussians / get_gaussian_params
  * (mtgs_scene_graph.py:457-459, 493-495) -- `crop_ids = crop_box.within(means)`, then `v[crop_ids]` per collected tensor.
- * Additive block: MTGS_RAST_ABI_VERSION stays 28 and MTGS_RAST_HOT_ABI_VERSION 7 (no existing kernel or signature changes).
+ * Additive block: it changed neither MTGS_RAST_ABI_VERSION nor MTGS_RAST_HOT_ABI_VERSION (no existing kernel or signature changes).
  * It is a header of its own, included by mtgs_rast.h: tests/golden/abi_signatures.txt is the reviewed record of mtgs_rast.h's
  * own declarations, and this block has its record in tests/golden/abi_signatures_crop.txt.  Conventions (device pointers
  * unless marked HOST, `stream`, return codes, mtgs_rast_last_error) are mtgs_rast.h's.

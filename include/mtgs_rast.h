@@ -34,13 +34,14 @@
 #include <stdint.h>
 
 #include "mtgs_crop.h"   /* additive block of its own: the crop box (mtgs_crop_select, mtgs_crop_gather) */
-#include "mtgs_refine_scene.h"   /* additive block of its own: refinement_after for a whole scene graph in one pass */
+#include "mtgs_refine_scene.h"   /* a block of its own: refinement_after for one node or a whole scene graph in one pass */
 
 #ifdef __cplusplus
 extern "C" {
 #endif
 
-#define MTGS_RAST_ABI_VERSION 28
+/* 29: mtgs_refine_classify / mtgs_refine_apply / mtgs_refine_rows are gone; one node is the one-entry table of mtgs_refine_scene.h */
+#define MTGS_RAST_ABI_VERSION 29
 /* Version of the HOT-PATH subset (mtgs_sh_*, mtgs_vis_color_*_dirs, mtgs_front_fwd, mtgs_bin3_build, mtgs_blend_*_packed, mtgs_project_bwd*): bumped only
  * when one of THOSE kernels or signatures changes, so that committed per-kernel counter files (profiles/rNN_pmc_step.json, keyed
  * on it) survive bumps of the optimizer / loss / node entry points.  mtgs_rast_hot_version() returns it. */
@@ -311,29 +312,6 @@ int mtgs_deform_embed(int64_t N, const float *means, float height, float t, cons
 int mtgs_fourier_dc_fwd(int64_t N, int F, const float *features_dc, const float *w, float *dc, void *stream);
 int mtgs_fourier_dc_bwd(int64_t N, int F, const float *features_dc, const float *w, const float *v_dc,
                         float *v_features_dc, float *partial_w, void *stream);
-
-/* ---- densification of a Gaussian node on the device (csrc/refine.hip) -------------------
- * Restates refinement_after / split_gaussians / dup_gaussians / cull_gaussians + the optimizer surgery of
- * mtgs/scene_model/gaussian_model/vanilla_gaussian_splatting.py:392-446, 476-699.
- * thresholds (HOST float[6]): densify_grad_thresh, densify_size_thresh, split_screen_size, cull_alpha_thresh,
- *   cull_scale_thresh, cull_screen_size.  options (HOST int[5]): n_split_samples (1..4), split by screen size
- *   (step < stop_screen_size_at), cull by world size (step > refine_every * reset_alpha_every), cull by screen size,
- *   clone_sample_means.  Samples: Philox4x32-10 keyed by (seed, step, Gaussian index, sample) -- identical on every rank.
- * mtgs_refine_classify: counts[(2 + n_split_samples), N] i32 (old row kept | child of sample s kept | duplicate kept),
- *   flags[N] u8.  The caller takes exclusive prefix sums of the count columns (pos, i64) and the first output row of each
- *   column's block (bases: old rows, then children sample-major, then duplicates -- the reference's order) and the total.
- * mtgs_refine_apply: src_index[n_out] i32 / kind[n_out] u8 of every output row and out_means / out_scales[n_out,3].
- * mtgs_refine_rows: dst[n_out,width] = src[src_index,:]; zero_new: rows of new Gaussians are zero (Adam moments). */
-int mtgs_refine_classify(int64_t N, const float *means, const float *scales, const float *quats,
-                         const float *opacities, const float *grad_norm, const float *vis_counts,
-                         const float *max_2dsize, const float *thresholds, const int *options, uint64_t seed,
-                         int64_t step, int32_t *counts, uint8_t *flags, void *stream);
-int mtgs_refine_apply(int64_t N, int64_t n_out, const uint8_t *flags, const int64_t *pos, const int64_t *bases,
-                      const float *means, const float *scales, const float *quats, const float *thresholds,
-                      const int *options, uint64_t seed, int64_t step, int32_t *src_index, uint8_t *kind,
-                      float *out_means, float *out_scales, void *stream);
-int mtgs_refine_rows(int64_t n_out, int64_t width, const float *src, const int32_t *src_index, const uint8_t *kind,
-                     int zero_new, float *dst, void *stream);
 
 /* ---- fused rasterization front end + binning (ABI v7; what mtgs_amd.wrapper._FusedRasterization runs) ------------
  * The gsplat-shaped operators above stay; these entry points run the same stages of gsplat.rendering.rasterization
@@ -884,7 +862,7 @@ int mtgs_rows_expand(int64_t N, int width, const int32_t *row_of, const float *r
                      void *stream);
 
 /* ---- WildGaussians appearance colours (config/WildGaussians.py; mtgs_scene_graph.py:308-318, :623-632) ----
- * Additive block: MTGS_RAST_ABI_VERSION stays 28 and MTGS_RAST_HOT_ABI_VERSION 7 (no existing kernel or signature changes).
+ * Additive block: it changed neither MTGS_RAST_ABI_VERSION nor MTGS_RAST_HOT_ABI_VERSION (no existing kernel or signature changes).
  *   rgb = clamp(features_dc * C0 + 0.5, 0, 1);  x = [rgb | features_rest row[:24] | e];  y = 0.01 * L3(relu(L2(relu(L1(x)))));
  *   colour = rgb * (1 + y[3:6]) + y[0:3]          (L1: 59 -> 128, L2: 128 -> 128, L3: 128 -> 6, nn.Linear layouts, fp32)
  * Weights are nn.Linear's: w1 [128, 59], b1 [128], w2 [128, 128], b2 [128], w3 [6, 128], b3 [6]; embedding e [32] (nullable:
@@ -917,7 +895,7 @@ int mtgs_wild_reduce(int64_t cap_rows, const float *partials, const float *embed
                      float *d_embed, void *stream);
 
 /* ---- Image metrics of get_metrics_dict (mtgs_scene_graph.py:747-804; mtgs/utils/pnsr.py color_correct, MaskedPSNR) ----
- * Additive block: MTGS_RAST_ABI_VERSION stays 28 and MTGS_RAST_HOT_ABI_VERSION 7 (no existing kernel or signature changes).
+ * Additive block: it changed neither MTGS_RAST_ABI_VERSION nor MTGS_RAST_HOT_ABI_VERSION (no existing kernel or signature changes).
  * Images are dense [P, 3] fp32 (P = H * W pixels), mask a nullable [P] uint8 (0 = masked out; NULL = every pixel).
  * mtgs_color_correct: out [P, 3] = color_correct(img * mask, ref * mask, num_iters, eps) -- per channel c, num_iters fits of
  *   a(x) = [x0^2, x0x1, x0x2, x1^2, x1x2, x2^2, x0, x1, x2, 1] . w_c to ref_c over the rows with unclipped(img_c) & unclipped(x_c)
@@ -937,7 +915,7 @@ int mtgs_image_metrics(int64_t P, int num_iters, double eps, const float *pred, 
                        const float *pred_depth, const float *lidar_depth, float *metrics, void *ws, size_t ws_bytes, void *stream);
 
 /* ---- Geometric loss terms of get_loss_dict (mtgs_scene_graph.py:905-940, 969-981; mtgs/utils/geometric_loss.py:350-388) ----
- * Additive block: MTGS_RAST_ABI_VERSION stays 28 and MTGS_RAST_HOT_ABI_VERSION 7 (no existing kernel or signature changes).
+ * Additive block: it changed neither MTGS_RAST_ABI_VERSION nor MTGS_RAST_HOT_ABI_VERSION (no existing kernel or signature changes).
  * Images are dense row-major: depth [H, W] fp32, normals [H, W, 3] fp32, mask a nullable [H, W] uint8 (0 = masked out).
  * K: DEVICE pointer to the 3x3 intrinsics, row-major fp32; fx, fy, cx, cy = K[0], K[4], K[2], K[5] are read by the kernels.
  * mtgs_depth_normals: out = (1 + n @ diag(1,-1,-1)) / 2 with n = normal_from_depth_image(depth, fx, fy, cx, cy, (W, H), eye(4)):
@@ -978,7 +956,7 @@ int mtgs_scale_reg_fwd(int64_t n, const float *scales, int two_d, float max_rati
 int mtgs_scale_reg_bwd(int64_t n, const float *scales, int two_d, float max_ratio, const float *v_out, float *v_scales, void *stream);
 
 /* ---- Pseudo-depth supervision of get_loss_dict (mtgs_scene_graph.py:844-873; mtgs/utils/geometric_loss.py:16-256) ----
- * Additive block: MTGS_RAST_ABI_VERSION stays 28 and MTGS_RAST_HOT_ABI_VERSION 7 (no existing kernel or signature changes).
+ * Additive block: it changed neither MTGS_RAST_ABI_VERSION nor MTGS_RAST_HOT_ABI_VERSION (no existing kernel or signature changes).
  * Images are dense row-major: pred, gt [H, W] fp32, rgb [H, W, 3] fp32 (read by EDGE_AWARE_LOG_L1 only, otherwise nullable),
  * mask a nullable [H, W] uint8 (0 = masked out).  m = (gt > lo) & (gt < hi) & mask (strict, fp32; HUBER_L1 also requires
  * gt != 0), e = pred - gt, n = count(m).  The value of `kind` ("scalar" implementation of the reference):
@@ -1035,7 +1013,7 @@ int mtgs_seed_fwd(int64_t N, int k, const float *knn_dist, const float *rgb, con
 
 /* ---- preparing the seeding point cloud (mtgs_amd/csrc/cloud.hip): NuPlanDataparser._load_3D_points
  * (mtgs/dataset/nuplan_dataparser.py:460-500) without open3d: remove_statistical_outlier and voxel_down_sample on the device.
- * Additive block: MTGS_RAST_ABI_VERSION stays 28 and MTGS_RAST_HOT_ABI_VERSION 7 (no existing kernel or signature changes).
+ * Additive block: it changed neither MTGS_RAST_ABI_VERSION nor MTGS_RAST_HOT_ABI_VERSION (no existing kernel or signature changes).
  * points: rows of three floats, row_stride floats apart (>= 3), so a [N, 4][:, :3] view is read in place.  0 <= N < 2^31;
  * N = 0 is a no-op.  ws: *_workspace_bytes(...) bytes, 16-byte aligned, no initialisation.  No host reads, no allocation, no
  * float atomics; the host checks name the bad argument (mtgs_rast_last_error).
@@ -1067,7 +1045,7 @@ int mtgs_cloud_voxel(int64_t N, double voxel_size, const float *points, int64_t 
 /* ---- SURVEY.md section 8f, rank 2 (second half): the optimizer step of every Gaussian parameter group in ONE launch ----
  * Reference: one torch.optim.Adam per parameter group with one tensor each (mtgs/scene_model/custom_trainer.py:115-136;
  * groups, learning rates and eps = 1e-15 in mtgs/config/MTGS.py:121-181); the densification moves the moments with their
- * rows (vanilla_gaussian_splatting.py:392-446 -> mtgs_refine_rows).  Arithmetic = torch.optim.Adam (amsgrad = False,
+ * rows (vanilla_gaussian_splatting.py:392-446 -> mtgs_refine_scene_rows).  Arithmetic = torch.optim.Adam (amsgrad = False,
  * maximize = False) in fp32:  g = grad_scale * g + weight_decay * p;  m += (g - m)(1 - beta1);  v = beta2 v + (1 - beta2) g^2;
  * p -= step_size * m / (sqrt(v) / bc2_sqrt + eps)  with step_size = lr / (1 - beta1^t), bc2_sqrt = sqrt(1 - beta2^t) computed
  * by the caller in double for the step t being taken and passed as `hyper[.][4]` = {step_size f32, bc2_sqrt f32, t i32,

@@ -8,11 +8,13 @@
 extern "C" {
 #endif
 
-/* ---- refinement_after for EVERY node of a scene graph in one pass (mtgs_amd/csrc/refine.hip; mtgs_amd.densify.refine_scene):
- * vanilla_gaussian_splatting.py:476-577 per node, with the node's own thresholds, seed, phase and cull rule
- * (skybox_gaussian_splatting.py:130-163: the sky node replaces the far rule's constants).
- * Additive block: MTGS_RAST_ABI_VERSION stays 28 and MTGS_RAST_HOT_ABI_VERSION 7 (mtgs_refine_classify / _apply / _rows and
- * their results do not change).  A header of its own, included by mtgs_rast.h; its reviewed record is
+/* ---- densification on the device: refinement_after for EVERY node of a scene graph in one pass (SURVEY.md section 8f, rank 2;
+ * mtgs_amd/csrc/refine.hip; mtgs_amd.densify.refine_scene, and refine_gaussians for ONE node: the one-entry case of the table).
+ * Restates refinement_after / split_gaussians / dup_gaussians / cull_gaussians + the optimizer surgery of
+ * mtgs/scene_model/gaussian_model/vanilla_gaussian_splatting.py:392-446, 476-699 per node, with the node's own thresholds, seed,
+ * phase and cull rule (skybox_gaussian_splatting.py:130-163: the sky node replaces the far rule's constants).
+ * The only refinement entry points since MTGS_RAST_ABI_VERSION 29, which removed the single-node mtgs_refine_classify / _apply /
+ * _rows; MTGS_RAST_HOT_ABI_VERSION stays 7.  A header of its own, included by mtgs_rast.h; its reviewed record is
  * tests/golden/abi_signatures_refine_scene.txt.  Conventions (device pointers unless marked HOST, `stream`, return codes,
  * mtgs_rast_last_error) are mtgs_rast.h's.
  *
@@ -21,13 +23,18 @@ extern "C" {
  * workgroups [first_block, first_block + ceil(n / 256)) of the classify and index launches.  A workgroup finds its node by
  * binary search over first_block.  Columns (kinds) of a node with S = options[0] split samples: 0 old row kept | 1 + s child
  * of sample s kept | 1 + S duplicate kept; the scene has n_columns = 2 + max S of them, a node's unused ones are zero.
- * thresholds / options: as mtgs_refine_classify.  Cull rule: far = |mean| > far_radius,
- * thresh = (far ? far_factor : 1) * cull_scale_thresh in fp32 (100 / 40: VanillaGaussianSplattingModel).
- * phase MTGS_REFINE_DENSIFY: mtgs_refine_classify's decisions, samples keyed by (seed, step, NODE-LOCAL index, slot).
+ * thresholds[6]: densify_grad_thresh, densify_size_thresh, split_screen_size, cull_alpha_thresh, cull_scale_thresh,
+ *   cull_screen_size.  options[5]: n_split_samples (1..4), split by screen size (step < stop_screen_size_at), cull by world size
+ *   (step > refine_every * reset_alpha_every), cull by screen size, clone_sample_means.  Cull rule: far = |mean| > far_radius,
+ *   thresh = (far ? far_factor : 1) * cull_scale_thresh in fp32 (100 / 40: VanillaGaussianSplattingModel).
+ * Flag byte of a Gaussian: bit 0 old row kept | bit 1 + s child of sample s kept | bit 1 + S duplicate kept | bit 7 split parent.
+ * phase MTGS_REFINE_DENSIFY: split / duplicate / cull; samples: Philox4x32-10 keyed by (seed, step, NODE-LOCAL index, slot) --
+ *   identical on every rank, and for a node alone or inside any scene.  Output order: old rows, then children sample-major, then
+ *   duplicates (the reference's).
  * phase MTGS_REFINE_CULL_ONLY: only column 0 can be 1 (cull_gaussians() without a split mask); the statistics pointers are
  *   not followed unless options[3] (screen-size rule), which reads max_2dsize.
  * mtgs_refine_scene_classify: counts[(n_columns + 1), n_total] i32 -- the columns above, then the split-parent bit -- and
- *   flags[n_total] u8 (mtgs_refine_classify's byte); parents (nullable, u8 [n_total]) = 1 where a child or the duplicate is
+ *   flags[n_total] u8 (the byte above); parents (nullable, u8 [n_total]) = 1 where a child or the duplicate is
  *   kept.  The caller takes an INCLUSIVE prefix sum of every counts row over the whole concatenation (incl, int64) and reads
  *   its values at the nodes' last elements: the one host read.  From them it fills, per node: scan_base[k] = incl[k] just
  *   before the node (0 for the first), col_base[k] = node-local first output row of column k, n_out, out_start (running sum

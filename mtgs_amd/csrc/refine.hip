@@ -1,7 +1,8 @@
-// refine.hip -- densification of one Gaussian node on the device: split / duplicate / cull with every per-Gaussian
-// tensor (parameters AND the optimizer's moment rows) compacted and appended by kernels, and the split / clone samples
-// drawn from a COUNTER-BASED generator keyed by (seed, step, Gaussian index, sample), so that every rank of a
-// data-parallel job -- whatever its launch geometry -- makes bit-identical decisions and rows.
+// refine.hip -- densification of the Gaussian nodes of a scene graph on the device (include/mtgs_refine_scene.h): split /
+// duplicate / cull with every per-Gaussian tensor (parameters AND the optimizer's moment rows) compacted and appended by
+// kernels, and the split / clone samples drawn from a COUNTER-BASED generator keyed by (node seed, step, node-local Gaussian
+// index, sample), so that every rank of a data-parallel job -- whatever its launch geometry -- makes bit-identical decisions
+// and rows.  The nodes come in a table in device memory; ONE node is the one-entry case of that table, there is no second path.
 //
 // Restates VanillaGaussianSplattingModel.refinement_after / split_gaussians / dup_gaussians / cull_gaussians and the
 // optimizer surgery dup_in_optim / remove_from_optim
@@ -16,9 +17,9 @@
 //   world-space / screen-space size limits (:585-612); moments: old rows follow, new rows start at zero (:418-437).
 // The result order is the reference's (boolean-mask order of that concatenation).
 //
-// Kernels: classify (per old Gaussian: what it becomes + how many rows survive), then -- after an exclusive scan of the
-// survivor counts -- index (source row and kind of every output row), geometry (means / scales of every output row) and
-// one generic row copy per remaining tensor.  Roofline: HBM (streaming + gathers), launch-bound at node sizes.
+// Kernels: classify (per old Gaussian: what it becomes + how many rows survive), then -- after an inclusive scan of the
+// survivor counts over all nodes -- index (source row and kind of every output row), geometry (means / scales of every output
+// row) and one table-driven launch that moves every remaining tensor of every node.  Roofline: HBM (streaming + gathers).
 #include "common.hpp"
 
 namespace {
@@ -96,104 +97,9 @@ __device__ __forceinline__ Node classify(const RefineCfg &c, int64_t i, const fl
     n.dup = (max_exp(n.sl_cur) <= c.size_thresh) && high;
     return n;
 }
-// flags: bit 0 old row kept | bit 1+s child s kept | bit 1+nsamps dup kept | bit 7 split
-__global__ __launch_bounds__(256) void refine_classify_kernel(int64_t N, const float *__restrict__ means, const float *__restrict__ scales,
-                                                             const float *__restrict__ quats, const float *__restrict__ opacities,
-                                                             const float *__restrict__ grad_norm, const float *__restrict__ vis_counts,
-                                                             const float *__restrict__ max2d, const RefineCfg c,
-                                                             int32_t *__restrict__ counts /* [2 + nsamps][N] */, uint8_t *__restrict__ flags) {
-    const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
-    if (i >= N) return;
-    const Node n = classify(c, i, means, scales, quats, opacities, grad_norm, vis_counts, max2d);
-    uint32_t f = n.split ? 0x80u : 0u;
-    if (!n.split && !culled(c, n.m, n.sl, n.opac, max2d[i])) f |= 1u;
-    for (int s = 0; s < c.nsamps; ++s) {
-        bool keep = false;
-        if (n.split) {
-            float z[3], cm[3];
-            refine_normal3(c, (uint32_t)i, (uint32_t)s, z);
-            sample_mean(n.m, n.sl, n.q, z, cm);
-            keep = !culled(c, cm, n.sl_cur, n.opac, 0.f);   // (new rows enter with max_2Dsize = 0, :517-524)
-        }
-        if (keep) f |= 2u << s;
-        counts[(int64_t)(1 + s) * N + i] = keep ? 1 : 0;
-    }
-    bool keep_dup = false;
-    if (n.dup) {
-        float dm[3] = {n.m[0], n.m[1], n.m[2]};
-        if (c.clone_sample_means) {
-            float z[3];
-            refine_normal3(c, (uint32_t)i, (uint32_t)c.nsamps, z);
-            sample_mean(n.m, n.sl_cur, n.q, z, dm);
-        }
-        keep_dup = !culled(c, dm, n.sl_cur, n.opac, 0.f);
-    }
-    if (keep_dup) f |= 2u << c.nsamps;
-    counts[i] = (int32_t)(f & 1u);
-    counts[(int64_t)(1 + c.nsamps) * N + i] = keep_dup ? 1 : 0;
-    flags[i] = (uint8_t)f;
-}
 
-// pos: EXCLUSIVE scans of the count columns, bases[k] = first output row of column k's block
-__global__ __launch_bounds__(256) void refine_index_kernel(int64_t N, int nsamps, const uint8_t *__restrict__ flags,
-                                                          const int64_t *__restrict__ pos /* [2 + nsamps][N] */,
-                                                          const int64_t *__restrict__ bases, int32_t *__restrict__ src_index,
-                                                          uint8_t *__restrict__ kind) {
-    const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
-    if (i >= N) return;
-    const uint32_t f = flags[i];
-    for (int k = 0; k < 2 + nsamps; ++k) {
-        if ((f >> k) & 1u) {
-            const int64_t row = bases[k] + pos[(int64_t)k * N + i];
-            src_index[row] = (int32_t)i;
-            kind[row] = (uint8_t)k;    // 0 old | 1 + s child of sample s | 1 + nsamps duplicate
-        }
-    }
-}
-
-__global__ __launch_bounds__(256) void refine_geometry_kernel(int64_t n_out, const int32_t *__restrict__ src_index,
-                                                             const uint8_t *__restrict__ kind, const uint8_t *__restrict__ flags,
-                                                             const float *__restrict__ means, const float *__restrict__ scales,
-                                                             const float *__restrict__ quats, const RefineCfg c,
-                                                             float *__restrict__ out_means, float *__restrict__ out_scales) {
-    const int64_t r = (int64_t)blockIdx.x * 256 + threadIdx.x;
-    if (r >= n_out) return;
-    const int64_t p = src_index[r];
-    const int k = kind[r];
-    float m[3], sl[3], sl_cur[3];
-#pragma unroll
-    for (int j = 0; j < 3; ++j) { m[j] = means[p * 3 + j]; sl[j] = scales[p * 3 + j]; }
-    const bool split = (flags[p] & 0x80u) != 0;
-#pragma unroll
-    for (int j = 0; j < 3; ++j) sl_cur[j] = split ? logf(expf(sl[j]) / kSplitShrink) : sl[j];
-    float om[3] = {m[0], m[1], m[2]};
-    if (k >= 1 && (k <= c.nsamps || c.clone_sample_means)) {
-        float z[3];
-        refine_normal3(c, (uint32_t)p, (uint32_t)(k - 1), z);
-        const float4 q = reinterpret_cast<const float4 *>(quats)[p];
-        if (k <= c.nsamps) sample_mean(m, sl, q, z, om);     // children: the parent's ORIGINAL scales spread the samples
-        else sample_mean(m, sl_cur, q, z, om);
-    }
-#pragma unroll
-    for (int j = 0; j < 3; ++j) {
-        out_means[r * 3 + j] = om[j];
-        out_scales[r * 3 + j] = k == 0 ? sl[j] : sl_cur[j];
-    }
-}
-
-// dst[r, :] = src[src_index[r], :]  (zero_new: rows that are not old rows become 0 -- optimizer moments of new Gaussians)
-__global__ __launch_bounds__(256) void refine_rows_kernel(int64_t n_out, int64_t w, const float *__restrict__ src,
-                                                         const int32_t *__restrict__ src_index, const uint8_t *__restrict__ kind,
-                                                         int zero_new, float *__restrict__ dst) {
-    const int64_t e = (int64_t)blockIdx.x * 256 + threadIdx.x;
-    if (e >= n_out * w) return;
-    const int64_t r = e / w, col = e - r * w;
-    dst[e] = (zero_new && kind[r] != 0) ? 0.f : src[(int64_t)src_index[r] * w + col];
-}
-
-// ---- the whole scene graph in one pass (include/mtgs_refine_scene.h) -------------------------------------------------------
-// The same decisions, samples and arithmetic as the kernels above (classify, culled, sample_mean, refine_normal3 are shared),
-// per node from a table in device memory: the node's thresholds, options, seed, cull rule and phase.  Gaussian indices are
+// ---- the kernels (include/mtgs_refine_scene.h) ---------------------------------------------------------------------------------
+// Per node from a table in device memory: the node's thresholds, options, seed, cull rule and phase.  Gaussian indices are
 // NODE-LOCAL everywhere (the Philox counter, src_index), so a node refines identically alone and inside any scene.
 static_assert(MTGS_REFINE_MAX_COLUMNS == 2 + MAX_SAMPS, "columns: old | MAX_SAMPS children | duplicate");
 
@@ -227,14 +133,14 @@ __global__ __launch_bounds__(256) void refine_scene_classify_kernel(const mtgs_r
     if (i >= d.n) return;
     const RefineCfg c = node_cfg(d, step);
     const int64_t g = d.start + i;
-    uint32_t f = 0u;
+    uint32_t f = 0u;                                   // bit 0 old row kept | bit 1+s child s kept | bit 1+nsamps dup kept | bit 7 split
     if (d.phase == MTGS_REFINE_CULL_ONLY) {            // cull_gaussians() without a split mask: rows only leave
         float m[3], sl[3];
 #pragma unroll
         for (int k = 0; k < 3; ++k) { m[k] = d.means[i * 3 + k]; sl[k] = d.scales[i * 3 + k]; }
         const float m2 = (c.cull_big && c.cull_screen) ? d.max_2dsize[i] : 0.f;
         if (!culled(c, m, sl, d.opacities[i], m2)) f = 1u;
-    } else {                                           // refine_classify_kernel, with the node-local index
+    } else {                                           // MTGS_REFINE_DENSIFY: the only statement of the decisions
         const Node n = classify(c, i, d.means, d.scales, d.quats, d.opacities, d.xys_grad_norm, d.vis_counts, d.max_2dsize);
         f = n.split ? 0x80u : 0u;
         if (!n.split && !culled(c, n.m, n.sl, n.opac, d.max_2dsize[i])) f |= 1u;
@@ -244,7 +150,7 @@ __global__ __launch_bounds__(256) void refine_scene_classify_kernel(const mtgs_r
                 float z[3], cm[3];
                 refine_normal3(c, (uint32_t)i, (uint32_t)s, z);
                 sample_mean(n.m, n.sl, n.q, z, cm);
-                keep = !culled(c, cm, n.sl_cur, n.opac, 0.f);
+                keep = !culled(c, cm, n.sl_cur, n.opac, 0.f);   // (new rows enter with max_2Dsize = 0, :517-524)
             }
             if (keep) f |= 2u << s;
         }
@@ -282,7 +188,7 @@ __global__ __launch_bounds__(256) void refine_scene_index_kernel(const mtgs_refi
             const int64_t local = d.col_base[k] + (incl[(int64_t)k * n_total + g] - 1 - d.scan_base[k]);
             if (local < 0 || local >= d.n_out) continue;      // (a table that does not belong to these scans: write nothing)
             src_index[d.out_start + local] = (int32_t)i;
-            kind[d.out_start + local] = (uint8_t)k;
+            kind[d.out_start + local] = (uint8_t)k;           // 0 old | 1 + s child of sample s | 1 + nsamps duplicate
         }
     }
 }
@@ -310,7 +216,7 @@ __global__ __launch_bounds__(256) void refine_scene_geometry_kernel(const mtgs_r
         float z[3];
         refine_normal3(c, (uint32_t)p, (uint32_t)(k - 1), z);
         const float4 q = reinterpret_cast<const float4 *>(d.quats)[p];
-        if (k <= c.nsamps) sample_mean(m, sl, q, z, om);
+        if (k <= c.nsamps) sample_mean(m, sl, q, z, om);     // children: the parent's ORIGINAL scales spread the samples
         else sample_mean(m, sl_cur, q, z, om);
     }
 #pragma unroll
@@ -409,63 +315,9 @@ __global__ __launch_bounds__(256) void refine_scene_rows_kernel(const mtgs_refin
     }
 }
 
-RefineCfg make_cfg(const float *th, const int *opt, uint64_t seed, int64_t step) {
-    RefineCfg c;
-    c.grad_thresh = th[0]; c.size_thresh = th[1]; c.split_screen_size = th[2]; c.cull_alpha_thresh = th[3];
-    c.cull_scale_thresh = th[4]; c.cull_screen_size = th[5];
-    c.nsamps = opt[0]; c.use_screen_split = opt[1]; c.cull_big = opt[2]; c.cull_screen = opt[3]; c.clone_sample_means = opt[4];
-    c.seed_lo = (uint32_t)seed; c.seed_hi = (uint32_t)(seed >> 32); c.step = (uint32_t)step;
-    c.far_radius = 100.f; c.far_factor = 40.f;      // VanillaGaussianSplattingModel.cull_gaussians (:599-600)
-    return c;
-}
-
 }  // namespace
 
-extern "C" int mtgs_refine_classify(int64_t N, const float *means, const float *scales, const float *quats,
-                                    const float *opacities, const float *grad_norm, const float *vis_counts,
-                                    const float *max_2dsize, const float *thresholds, const int *options, uint64_t seed,
-                                    int64_t step, int32_t *counts, uint8_t *flags, void *stream) {
-    MTGS_REQUIRE(N >= 0 && N < ((int64_t)1 << 31) && thresholds && options, MTGS_EINVAL, "mtgs_refine_classify: bad arguments");
-    MTGS_REQUIRE(options[0] >= 1 && options[0] <= MAX_SAMPS, MTGS_EUNSUPPORTED, "mtgs_refine_classify: n_split_samples=%d (1..%d)",
-                 options[0], MAX_SAMPS);
-    if (N == 0) return MTGS_OK;
-    MTGS_REQUIRE(means && scales && quats && opacities && grad_norm && vis_counts && max_2dsize && counts && flags, MTGS_EINVAL,
-                 "mtgs_refine_classify: null pointer");
-    refine_classify_kernel<<<(unsigned)ceil_div64(N, 256), 256, 0, (hipStream_t)stream>>>(
-        N, means, scales, quats, opacities, grad_norm, vis_counts, max_2dsize, make_cfg(thresholds, options, seed, step), counts, flags);
-    MTGS_CHECK_LAUNCH("mtgs_refine_classify");
-    return MTGS_OK;
-}
-
-extern "C" int mtgs_refine_apply(int64_t N, int64_t n_out, const uint8_t *flags, const int64_t *pos, const int64_t *bases,
-                                 const float *means, const float *scales, const float *quats, const float *thresholds,
-                                 const int *options, uint64_t seed, int64_t step, int32_t *src_index, uint8_t *kind,
-                                 float *out_means, float *out_scales, void *stream) {
-    MTGS_REQUIRE(N >= 0 && n_out >= 0 && n_out < ((int64_t)1 << 31) && thresholds && options, MTGS_EINVAL, "mtgs_refine_apply: bad arguments");
-    if (N == 0 || n_out == 0) return MTGS_OK;
-    MTGS_REQUIRE(flags && pos && bases && means && scales && quats && src_index && kind && out_means && out_scales, MTGS_EINVAL,
-                 "mtgs_refine_apply: null pointer");
-    const RefineCfg c = make_cfg(thresholds, options, seed, step);
-    hipStream_t st = (hipStream_t)stream;
-    refine_index_kernel<<<(unsigned)ceil_div64(N, 256), 256, 0, st>>>(N, c.nsamps, flags, pos, bases, src_index, kind);
-    refine_geometry_kernel<<<(unsigned)ceil_div64(n_out, 256), 256, 0, st>>>(n_out, src_index, kind, flags, means, scales, quats, c,
-                                                                          out_means, out_scales);
-    MTGS_CHECK_LAUNCH("mtgs_refine_apply");
-    return MTGS_OK;
-}
-
-extern "C" int mtgs_refine_rows(int64_t n_out, int64_t width, const float *src, const int32_t *src_index, const uint8_t *kind,
-                                int zero_new, float *dst, void *stream) {
-    MTGS_REQUIRE(n_out >= 0 && width >= 0, MTGS_EINVAL, "mtgs_refine_rows: bad sizes");
-    if (n_out * width == 0) return MTGS_OK;
-    MTGS_REQUIRE(src && src_index && kind && dst, MTGS_EINVAL, "mtgs_refine_rows: null pointer");
-    refine_rows_kernel<<<(unsigned)ceil_div64(n_out * width, 256), 256, 0, (hipStream_t)stream>>>(n_out, width, src, src_index, kind,
-                                                                                               zero_new, dst);
-    MTGS_CHECK_LAUNCH("mtgs_refine_rows");
-    return MTGS_OK;
-}
-
-// ---- the scene-wide entry points (include/mtgs_refine_scene.h) ---------------------------------------------------------------
+// ---- the entry points (include/mtgs_refine_scene.h) --------------------------------------------------------------------------
 extern "C" int mtgs_refine_scene_table_bytes(size_t *node_bytes, size_t *move_bytes) {
     MTGS_REQUIRE(node_bytes, MTGS_EINVAL, "mtgs_refine_scene_table_bytes: null pointer: node_bytes");
     MTGS_REQUIRE(move_bytes, MTGS_EINVAL, "mtgs_refine_scene_table_bytes: null pointer: move_bytes");

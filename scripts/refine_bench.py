@@ -1,5 +1,5 @@
-"""Times mtgs_amd.densify.refine_scene against the loop it replaces -- refine_gaussians + reset_opacities per node -- on the same
-seeded scenes, in one process, the two alternating, every timed call ending in a device synchronisation (host clock: the host
+"""Times mtgs_amd.densify.refine_scene against the loop it replaces -- refine_gaussians + reset_opacities per node, each call a
+pass over a table of one node -- on the same seeded scenes, in one process, the two alternating, every timed call ending in a device synchronisation (host clock: the host
 work between the launches is what the per-node loop pays for).
 
     python scripts/refine_bench.py [--out profiles/refine_scene.txt] [--repeats 9] [--small]
@@ -138,14 +138,14 @@ def main():
             for _ in range(3):
                 refine_scene(nodes, STEP)
             t_sky = [timed(lambda: refine_scene(nodes, STEP))[0] for _ in range(args.repeats)]
-        _lib.time_calls(["mtgs_refine_scene_rows", "mtgs_refine_rows"])
+        _lib.time_calls(["mtgs_refine_scene_rows"])
         refine_scene(same, STEP)
         torch.cuda.synchronize()
         rows_scene = sum(_lib.timed_ms()["mtgs_refine_scene_rows"])
-        _lib.time_calls(["mtgs_refine_scene_rows", "mtgs_refine_rows"])
-        loop(same, STEP)
+        _lib.time_calls(["mtgs_refine_scene_rows"])
+        loop(same, STEP)                                   # (one launch per node: refine_gaussians is the one-entry table)
         torch.cuda.synchronize()
-        rows_loop = _lib.timed_ms()["mtgs_refine_rows"]
+        rows_loop = _lib.timed_ms()["mtgs_refine_scene_rows"]
         _lib.time_calls(())
         med_l, med_s = statistics.median(t_loop), statistics.median(t_scene)
         noise = max(max(t_loop) - min(t_loop), max(t_scene) - min(t_scene))
@@ -156,7 +156,7 @@ def main():
             lines.append(f"  refine_scene, sky node by its own rule (100, 1000): {spread(t_sky)}")
         lines += [f"  difference of the medians {med_l - med_s:+.2f} ms (loop - scene); largest spread (max - min) of either {noise:.2f} ms",
                   f"  row move: {nbytes / 1e9:.3f} GB counted from the shapes; refine_scene ONE launch {rows_scene:.3f} ms = {nbytes / rows_scene / 1e6:.0f} GB/s; "
-                  f"loop {len(rows_loop)} launches of mtgs_refine_rows {sum(rows_loop):.3f} ms = {nbytes / sum(rows_loop) / 1e6:.0f} GB/s (device time, HIP events)"]
+                  f"loop {len(rows_loop)} launches of mtgs_refine_scene_rows {sum(rows_loop):.3f} ms = {nbytes / sum(rows_loop) / 1e6:.0f} GB/s (device time, HIP events)"]
         verdict[which] = (med_l - med_s, noise)
         del nodes, same
         torch.cuda.empty_cache()

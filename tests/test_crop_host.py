@@ -167,7 +167,7 @@ def test_within_agrees_with_the_nerfstudio_shaped_evaluation():
 def test_the_entry_points_are_declared_and_bound(hip_lib):
     """The crop block is include/mtgs_crop.h, which mtgs_rast.h includes; mtgs_amd._abi reads it with the parser of the main
     header and mtgs_amd._lib binds what it declares.  Its reviewed record is tests/golden/abi_signatures_crop.txt (same spelling
-    as tests/golden/abi_signatures.txt, which stays the record of mtgs_rast.h's own declarations).  The ABI versions are unchanged."""
+    as tests/golden/abi_signatures.txt, which stays the record of mtgs_rast.h's own declarations).  The crop block itself never changed the ABI versions."""
     import re
     from pathlib import Path
     from mtgs_amd import _abi, _lib
@@ -185,8 +185,8 @@ def test_the_entry_points_are_declared_and_bound(hip_lib):
         assert hasattr(raw, name), f"{name} not exported by libmtgs_rast.so"
         fn = getattr(hip_lib, name)
         assert fn.restype is C.c_int is restype and list(fn.argtypes) == argtypes
-    assert _abi.constant("MTGS_RAST_ABI_VERSION") == 28 and _abi.constant("MTGS_RAST_HOT_ABI_VERSION") == 7
-    assert hip_lib.mtgs_rast_version() == 28 and hip_lib.mtgs_rast_hot_version() == 7
+    assert _abi.constant("MTGS_RAST_ABI_VERSION") == 29 and _abi.constant("MTGS_RAST_HOT_ABI_VERSION") == 7
+    assert hip_lib.mtgs_rast_version() == 29 and hip_lib.mtgs_rast_hot_version() == 7
 
 
 def test_host_side_argument_checks(hip_lib):

@@ -592,9 +592,11 @@ def test_refinement_moves_extras_and_calls_the_hook_once(hip_lib):
 def test_refinement_refuses_unsupported_sample_counts(hip_lib, S, hook):
     from mtgs_amd.densify import RefineConfig, refine_gaussians
     p, stats, _ = refine_inputs(REFINE_BY_NAME["N257-S2"])
-    with pytest.raises(RuntimeError, match="mtgs_refine_classify"):
+    calls = []
+    with pytest.raises(RuntimeError, match="n_split_samples"):
         refine_gaussians({k: v.cuda() for k, v in p.items()}, tuple(s.cuda() for s in stats), RefineConfig(n_split_samples=S),
-                         REFINE_STEP, REFINE_SEED, before_rows=(lambda m: None) if hook else None)
+                         REFINE_STEP, REFINE_SEED, before_rows=calls.append if hook else None)
+    assert not calls
 
 
 # ---- out-of-box regulariser -----------------------------------------------------------------------------------------------------

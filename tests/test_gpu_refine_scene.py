@@ -207,6 +207,74 @@ def test_reset_step_equals_refine_then_reset_opacities(hip_lib):
     assert clamped > 5000
 
 
+@pytest.mark.parametrize("N", [257, 4000])
+def test_refine_gaussians_ignores_the_scene_gates(hip_lib, N):
+    """refine_gaussians is the one-entry table with the phase forced to densify: with stop_split_at = 100 at step 4000 -- past the
+    split phase, where refine_scene leaves the node untouched -- it returns the bits of the same call with the default stop_split_at."""
+    from mtgs_amd.densify import refine_gaussians, refine_scene
+    step, i = 4000, R.IDENTITY_SIZES.index(N)
+    nd = identity_nodes()[i]
+    late = replace(nd.cfg, stop_split_at=100)
+    assert refine_scene([replace(nd, cfg=late)], step) == [None]
+    seen = []
+    got = refine_gaussians(nd.params, nd.stats, late, step, nd.seed, moments=nd.moments, extras=nd.extras, before_rows=seen.append)
+    want = per_node(step, i)
+    assert got[2]["n_before"] == N and got[2]["n_children"] + got[2]["n_dups"] > 0
+    assert_same(got, want[:3], N)
+    assert len(seen) == 1 and torch.equal(seen[0], want[3])
+
+
+def test_refine_gaussians_alone_does_not_reset(hip_lib):
+    """At the reset step refine_gaussians clamps nothing and zeroes no moment: the reset is reset_opacities, the caller's.  (The
+    reset test above applies reset_opacities to its result, which would hide a reset that had already happened.)"""
+    from mtgs_amd.densify import refine_gaussians
+    step = R.RESET_STEP
+    for N in (257, 4000):
+        nd = identity_nodes()[R.IDENTITY_SIZES.index(N)]
+        new, new_m, info = refine_gaussians(nd.params, nd.stats, nd.cfg, step, nd.seed, moments=nd.moments, extras=nd.extras)
+        cap = np.float32(np.log(2 * nd.cfg.cull_alpha_thresh / (1 - 2 * nd.cfg.cull_alpha_thresh)))
+        assert float(new["opacities"].max()) > cap
+        old = info["kind"] == 0
+        src = info["src_index"][old].long()
+        assert int(old.sum()) == info["n_old_kept"] > 0
+        for h in (0, 1):
+            assert torch.equal(new_m["opacities"][h][old].view(torch.int32), nd.moments["opacities"][h][src].view(torch.int32)), (N, h)
+        assert torch.equal(new["opacities"][old].view(torch.int32), nd.params["opacities"][src].view(torch.int32)), N
+
+
+def test_an_empty_node_costs_no_launch_and_no_host_read(hip_lib):
+    """N == 0: every tensor is (0, ...), every count 0, and -- under torch.cuda.set_sync_debug_mode("warn") -- no synchronisation
+    warning.  Skipped only if the mode does not report a deliberate .item() on this build."""
+    from mtgs_amd.densify import refine_gaussians
+    nd = identity_nodes()[R.IDENTITY_SIZES.index(0)]
+    assert nd.params["means"].shape[0] == 0
+    torch.cuda.synchronize()
+    prior = torch.cuda.get_sync_debug_mode()
+    torch.cuda.set_sync_debug_mode("warn")
+    try:
+        with warnings.catch_warnings(record=True) as probe:
+            warnings.simplefilter("always")
+            torch.ones(1, device="cuda").item()
+        if not any("synchroniz" in str(w.message).lower() for w in probe):
+            pytest.skip("torch.cuda.set_sync_debug_mode('warn') does not report a deliberate .item() on this build")
+        calls = []
+        with warnings.catch_warnings(record=True) as seen:
+            warnings.simplefilter("always")
+            new, new_m, info = refine_gaussians(nd.params, nd.stats, nd.cfg, 4000, nd.seed, moments=nd.moments, extras=nd.extras,
+                                                before_rows=calls.append)
+    finally:
+        torch.cuda.set_sync_debug_mode(prior)
+    assert not [str(w.message) for w in seen if "synchroniz" in str(w.message).lower()] and not calls
+    assert [info[k] for k in COUNTS] == [0] * len(COUNTS) and all(isinstance(info[k], int) for k in COUNTS)
+    assert info["src_index"].shape == (0,) and info["src_index"].dtype == torch.int32 and info["kind"].shape == (0,) and info["kind"].dtype == torch.uint8
+    assert list(new) == list(nd.params) and set(new_m) == set(nd.moments) and set(info["extras"]) == set(nd.extras)
+    for k, t in nd.params.items():
+        assert new[k].shape == (0,) + tuple(t.shape[1:]) and new[k].dtype == torch.float32 and new[k].is_cuda, k
+        assert new_m[k][0].shape == new_m[k][1].shape == new[k].shape, k
+    for k, t in nd.extras.items():
+        assert info["extras"][k].shape == (0,) + tuple(t.shape[1:]) and info["extras"][k].dtype == t.dtype, k
+
+
 def test_deterministic_and_independent_of_the_neighbours(hip_lib):
     """Two calls give identical bits; a node's result does not depend on which other nodes are in the scene, or where it stands."""
     from mtgs_amd.densify import refine_scene

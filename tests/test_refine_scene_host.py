@@ -120,7 +120,7 @@ NAMES = ["mtgs_refine_scene_apply", "mtgs_refine_scene_classify", "mtgs_refine_s
 def test_the_header_is_declared_bound_and_exported(hip_lib):
     """include/mtgs_refine_scene.h is included by mtgs_rast.h, read by mtgs_amd._abi.header_abi and bound by mtgs_amd._lib as a
     group of its own: it joins neither mtgs_rast.h's own record nor the extension headers'.  Its reviewed record is
-    tests/golden/abi_signatures_refine_scene.txt.  The ABI versions are unchanged."""
+    tests/golden/abi_signatures_refine_scene.txt.  The ABI version is 29: the one that removed the single-node entry points."""
     from mtgs_amd import _abi, _lib, densify
     abi = _abi.header_abi("mtgs_refine_scene.h")
     frozen = (ROOT / "tests" / "golden" / "abi_signatures_refine_scene.txt").read_text()
@@ -145,8 +145,8 @@ def test_the_header_is_declared_bound_and_exported(hip_lib):
     assert (nb.value, mb.value) == (densify._REFINE_NODE.itemsize, densify._REFINE_MOVE.itemsize) == (264, 64)
     assert densify._REFINE_NODE == abi.structs["mtgs_refine_node"] and densify._REFINE_MOVE == abi.structs["mtgs_refine_move"]
     assert abi.constants["MTGS_REFINE_MAX_COLUMNS"] == 6 and (abi.constants["MTGS_REFINE_DENSIFY"], abi.constants["MTGS_REFINE_CULL_ONLY"]) == (1, 2)
-    assert _abi.constant("MTGS_RAST_ABI_VERSION") == 28 and _abi.constant("MTGS_RAST_HOT_ABI_VERSION") == 7
-    assert hip_lib.mtgs_rast_version() == 28 and hip_lib.mtgs_rast_hot_version() == 7
+    assert _abi.constant("MTGS_RAST_ABI_VERSION") == 29 and _abi.constant("MTGS_RAST_HOT_ABI_VERSION") == 7
+    assert hip_lib.mtgs_rast_version() == 29 and hip_lib.mtgs_rast_hot_version() == 7
 
 
 def test_the_c_compiler_lays_the_tables_out_as_the_reader_does(tmp_path):

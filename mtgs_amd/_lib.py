@@ -34,6 +34,9 @@ EXTENSION_EXPORTS = list(_EXTENSION_PROTOTYPES)
 REFINE_SCENE_HEADER = "mtgs_refine_scene.h"             # a third group, with a record of its own (densify.refine_scene)
 _REFINE_SCENE_PROTOTYPES = _abi.header_abi(REFINE_SCENE_HEADER).prototypes
 REFINE_SCENE_EXPORTS = list(_REFINE_SCENE_PROTOTYPES)
+PRESENT_HEADER = "mtgs_present.h"                       # a fourth group, with a record of its own (mtgs_amd.present)
+_PRESENT_PROTOTYPES = _abi.header_abi(PRESENT_HEADER).prototypes
+PRESENT_EXPORTS = list(_PRESENT_PROTOTYPES)
 ABI_VERSION = _abi.constant("MTGS_RAST_ABI_VERSION")
 HOT_ABI_VERSION = _abi.constant("MTGS_RAST_HOT_ABI_VERSION")      # hot-path subset: what profiles/rNN_pmc_step.json is keyed on
 
@@ -50,7 +53,7 @@ def load() -> C.CDLL:
             f"{LIB_PATH} is missing: build it with `python -m mtgs_amd.build` (needs hipcc). "
             "mtgs_amd has no CPU or PyTorch fallback for the rasterizer.")
     lib = C.CDLL(str(LIB_PATH))
-    for name, (restype, argtypes) in {**_PROTOTYPES, **_EXTENSION_PROTOTYPES, **_REFINE_SCENE_PROTOTYPES}.items():
+    for name, (restype, argtypes) in {**_PROTOTYPES, **_EXTENSION_PROTOTYPES, **_REFINE_SCENE_PROTOTYPES, **_PRESENT_PROTOTYPES}.items():
         fn = getattr(lib, name)
         fn.argtypes = argtypes
         fn.restype = restype

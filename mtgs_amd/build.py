@@ -28,10 +28,11 @@ COMMON_FLAGS = [
 # The projection forward must round after every operation (bit-exact tile binning inputs); the metrics and the
 # geometric and depth losses round as the reference's per-operation PyTorch kernels do, and so do the neighbour distances, the seeding
 # and the point-cloud filters (whose fp64 sums and voxel indices are compared bit for bit with a NumPy transcription); the crop box
-# decides a row by three fp32 dot products that the host evaluates operation by operation in torch and NumPy.
+# decides a row by three fp32 dot products that the host evaluates operation by operation in torch and NumPy;
+# the colormaps of a presented frame are nerfstudio's chain of element-wise fp32 kernels, one rounding per operation.
 PER_FILE_FLAGS = {"project.hip": ["-ffp-contract=off"], "front.hip": ["-ffp-contract=off"], "metrics.hip": ["-ffp-contract=off"],
                   "geomloss.hip": ["-ffp-contract=off"], "depthloss.hip": ["-ffp-contract=off"], "seed.hip": ["-ffp-contract=off"], "cloud.hip": ["-ffp-contract=off"],
-                  "crop.hip": ["-ffp-contract=off"]}
+                  "crop.hip": ["-ffp-contract=off"], "present.hip": ["-ffp-contract=off"]}
 
 
 class HipccNotFound(RuntimeError):

@@ -37,6 +37,9 @@ REFINE_SCENE_EXPORTS = list(_REFINE_SCENE_PROTOTYPES)
 PRESENT_HEADER = "mtgs_present.h"                       # a fourth group, with a record of its own (mtgs_amd.present)
 _PRESENT_PROTOTYPES = _abi.header_abi(PRESENT_HEADER).prototypes
 PRESENT_EXPORTS = list(_PRESENT_PROTOTYPES)
+LPIPS_HEADER = "mtgs_lpips.h"                           # a fifth group, with a record of its own (mtgs_amd.lpips)
+_LPIPS_PROTOTYPES = _abi.header_abi(LPIPS_HEADER).prototypes
+LPIPS_EXPORTS = list(_LPIPS_PROTOTYPES)
 ABI_VERSION = _abi.constant("MTGS_RAST_ABI_VERSION")
 HOT_ABI_VERSION = _abi.constant("MTGS_RAST_HOT_ABI_VERSION")      # hot-path subset: what profiles/rNN_pmc_step.json is keyed on
 
@@ -53,7 +56,8 @@ def load() -> C.CDLL:
             f"{LIB_PATH} is missing: build it with `python -m mtgs_amd.build` (needs hipcc). "
             "mtgs_amd has no CPU or PyTorch fallback for the rasterizer.")
     lib = C.CDLL(str(LIB_PATH))
-    for name, (restype, argtypes) in {**_PROTOTYPES, **_EXTENSION_PROTOTYPES, **_REFINE_SCENE_PROTOTYPES, **_PRESENT_PROTOTYPES}.items():
+    for name, (restype, argtypes) in {**_PROTOTYPES, **_EXTENSION_PROTOTYPES, **_REFINE_SCENE_PROTOTYPES, **_PRESENT_PROTOTYPES,
+                                      **_LPIPS_PROTOTYPES}.items():
         fn = getattr(lib, name)
         fn.argtypes = argtypes
         fn.restype = restype

@@ -37,6 +37,7 @@
 #include "mtgs_refine_scene.h"   /* a block of its own: refinement_after for one node or a whole scene graph in one pass */
 #include "mtgs_present.h"   /* a block of its own: colormaps, split / concatenated panels, uint8 frames and the viewer's resized depth */
 #include "mtgs_lpips.h"   /* a block of its own: the LPIPS metric (AlexNet): f32 MFMA convolutions, max-pools and the fused tail */
+#include "mtgs_dino.h"   /* a block of its own: the DINOv2 similarity metric: Pillow's resample, a ViT forward on f32 MFMA, the cosine tail */
 
 #ifdef __cplusplus
 extern "C" {

@@ -40,6 +40,9 @@ PRESENT_EXPORTS = list(_PRESENT_PROTOTYPES)
 LPIPS_HEADER = "mtgs_lpips.h"                           # a fifth group, with a record of its own (mtgs_amd.lpips)
 _LPIPS_PROTOTYPES = _abi.header_abi(LPIPS_HEADER).prototypes
 LPIPS_EXPORTS = list(_LPIPS_PROTOTYPES)
+DINO_HEADER = "mtgs_dino.h"                             # a sixth group, with a record of its own (mtgs_amd.dino)
+_DINO_PROTOTYPES = _abi.header_abi(DINO_HEADER).prototypes
+DINO_EXPORTS = list(_DINO_PROTOTYPES)
 ABI_VERSION = _abi.constant("MTGS_RAST_ABI_VERSION")
 HOT_ABI_VERSION = _abi.constant("MTGS_RAST_HOT_ABI_VERSION")      # hot-path subset: what profiles/rNN_pmc_step.json is keyed on
 
@@ -57,7 +60,7 @@ def load() -> C.CDLL:
             "mtgs_amd has no CPU or PyTorch fallback for the rasterizer.")
     lib = C.CDLL(str(LIB_PATH))
     for name, (restype, argtypes) in {**_PROTOTYPES, **_EXTENSION_PROTOTYPES, **_REFINE_SCENE_PROTOTYPES, **_PRESENT_PROTOTYPES,
-                                      **_LPIPS_PROTOTYPES}.items():
+                                      **_LPIPS_PROTOTYPES, **_DINO_PROTOTYPES}.items():
         fn = getattr(lib, name)
         fn.argtypes = argtypes
         fn.restype = restype

@@ -31,7 +31,8 @@ COMMON_FLAGS = [
 # decides a row by three fp32 dot products that the host evaluates operation by operation in torch and NumPy;
 # the colormaps of a presented frame are nerfstudio's chain of element-wise fp32 kernels, one rounding per operation.
 # lpips.hip (the LPIPS metric) takes the common flags: its convolutions are fma chains on the MFMA unit whatever the flag, and its
-# tail is compared with an fp64 restatement within a derived bound, not bit for bit.
+# tail is compared with an fp64 restatement within a derived bound, not bit for bit.  dino.hip (the DINOv2 similarity) likewise: its
+# preprocessing is integer arithmetic and single correctly rounded fp32 operations that no contraction can join.
 PER_FILE_FLAGS = {"project.hip": ["-ffp-contract=off"], "front.hip": ["-ffp-contract=off"], "metrics.hip": ["-ffp-contract=off"],
                   "geomloss.hip": ["-ffp-contract=off"], "depthloss.hip": ["-ffp-contract=off"], "seed.hip": ["-ffp-contract=off"], "cloud.hip": ["-ffp-contract=off"],
                   "crop.hip": ["-ffp-contract=off"], "present.hip": ["-ffp-contract=off"]}

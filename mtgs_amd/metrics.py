@@ -7,7 +7,8 @@ that mtgs_scene_graph.py's get_metrics_dict computes on every training step and 
 
 Forward only, no host reads (graph-capturable), bitwise reproducible.  The SSIM metric takes the loss's arguments
 (use_ssim_on_raw_rgb=True): reuse mtgs_amd.loss.masked_ssim.  LPIPS (AlexNet) is mtgs_amd.lpips, re-exported here: `lpips`, `LpipsWeights`, and
-image_metrics(..., lpips_weights=w)["lpips"].  DINOv2 stays in PyTorch.
+image_metrics(..., lpips_weights=w)["lpips"].  The DINOv2 similarity is mtgs_amd.dino, re-exported here: `dino_similarity`, `DinoWeights`,
+and image_metrics(..., dino_weights=w)["dinov2_sim"].
 """
 from __future__ import annotations
 
@@ -18,6 +19,7 @@ from torch import Tensor
 
 from ._lib import call, ptr, require_gpu, stream_of, workspace
 from .loss import _as_f32, _mask_u8
+from .dino import DinoWeights, dino_similarity
 from .lpips import LpipsWeights, lpips
 
 _EPS = 0.5 / 255
@@ -56,12 +58,13 @@ def color_correct(img: Tensor, ref: Tensor, mask: Optional[Tensor] = None, num_i
 
 def image_metrics(pred: Tensor, gt: Tensor, mask: Optional[Tensor] = None, *, color_corrected: bool = True,
                   pred_depth: Optional[Tensor] = None, lidar_depth: Optional[Tensor] = None,
-                  lpips_weights: Optional[LpipsWeights] = None) -> Dict[str, Tensor]:
+                  lpips_weights: Optional[LpipsWeights] = None, dino_weights: Optional[DinoWeights] = None) -> Dict[str, Tensor]:
     """get_metrics_dict's device metrics under MTGS's keys, as 0-dim fp32 tensors on pred's device:
     psnr = MaskedPSNR(data_range=1.0)(gt, pred, mask); cc_psnr (color_corrected) = the same of color_correct(pred * mask,
     gt * mask), without writing the corrected image; depth_RMSE, depth_absRel, depth_delta1 (both depths given) over the pixels
     with 0.1 < lidar < 80 and the mask.  Empty selections give nan, a zero error gives inf (as torch).
-    lpips (lpips_weights given) = lpips(pred, gt, mask, weights=lpips_weights), LPIPS(normalize=True) of gt * mask and pred * mask."""
+    lpips (lpips_weights given) = lpips(pred, gt, mask, weights=lpips_weights), LPIPS(normalize=True) of gt * mask and pred * mask.
+    dinov2_sim (dino_weights given) = dino_similarity(pred, gt, mask, weights=dino_weights), DINOv2Similarity.similarity(pred, gt, mask)."""
     _check_images(pred, gt, ("pred", "gt"))
     if (pred_depth is None) != (lidar_depth is None):
         raise ValueError("pred_depth and lidar_depth must be given together")
@@ -89,4 +92,6 @@ def image_metrics(pred: Tensor, gt: Tensor, mask: Optional[Tensor] = None, *, co
         res.update(depth_RMSE=out[2], depth_absRel=out[3], depth_delta1=out[4])
     if lpips_weights is not None:
         res["lpips"] = lpips(pred, gt, mask, weights=lpips_weights)
+    if dino_weights is not None:
+        res["dinov2_sim"] = dino_similarity(pred, gt, mask, weights=dino_weights)
     return res

@@ -43,6 +43,9 @@ LPIPS_EXPORTS = list(_LPIPS_PROTOTYPES)
 DINO_HEADER = "mtgs_dino.h"                             # a sixth group, with a record of its own (mtgs_amd.dino)
 _DINO_PROTOTYPES = _abi.header_abi(DINO_HEADER).prototypes
 DINO_EXPORTS = list(_DINO_PROTOTYPES)
+JPEG_HEADER = "mtgs_jpeg.h"                             # a seventh group, with a record of its own (mtgs_amd.jpeg)
+_JPEG_PROTOTYPES = _abi.header_abi(JPEG_HEADER).prototypes
+JPEG_EXPORTS = list(_JPEG_PROTOTYPES)
 ABI_VERSION = _abi.constant("MTGS_RAST_ABI_VERSION")
 HOT_ABI_VERSION = _abi.constant("MTGS_RAST_HOT_ABI_VERSION")      # hot-path subset: what profiles/rNN_pmc_step.json is keyed on
 
@@ -60,7 +63,7 @@ def load() -> C.CDLL:
             "mtgs_amd has no CPU or PyTorch fallback for the rasterizer.")
     lib = C.CDLL(str(LIB_PATH))
     for name, (restype, argtypes) in {**_PROTOTYPES, **_EXTENSION_PROTOTYPES, **_REFINE_SCENE_PROTOTYPES, **_PRESENT_PROTOTYPES,
-                                      **_LPIPS_PROTOTYPES, **_DINO_PROTOTYPES}.items():
+                                      **_LPIPS_PROTOTYPES, **_DINO_PROTOTYPES, **_JPEG_PROTOTYPES}.items():
         fn = getattr(lib, name)
         fn.argtypes = argtypes
         fn.restype = restype

@@ -33,6 +33,7 @@ COMMON_FLAGS = [
 # lpips.hip (the LPIPS metric) takes the common flags: its convolutions are fma chains on the MFMA unit whatever the flag, and its
 # tail is compared with an fp64 restatement within a derived bound, not bit for bit.  dino.hip (the DINOv2 similarity) likewise: its
 # preprocessing is integer arithmetic and single correctly rounded fp32 operations that no contraction can join.
+# jpeg.hip (the JPEG encoder) is integer arithmetic; its one fp32 conversion uses __fmul_rn / __fadd_rn, which never fuse.
 PER_FILE_FLAGS = {"project.hip": ["-ffp-contract=off"], "front.hip": ["-ffp-contract=off"], "metrics.hip": ["-ffp-contract=off"],
                   "geomloss.hip": ["-ffp-contract=off"], "depthloss.hip": ["-ffp-contract=off"], "seed.hip": ["-ffp-contract=off"], "cloud.hip": ["-ffp-contract=off"],
                   "crop.hip": ["-ffp-contract=off"], "present.hip": ["-ffp-contract=off"]}

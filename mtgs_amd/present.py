@@ -32,6 +32,7 @@ from torch import Tensor
 
 from . import _abi
 from ._lib import PRESENT_HEADER, call, ptr, require_gpu, stream_of
+from .jpeg import JpegStream, encode_jpeg
 
 _ABI = _abi.header_abi(PRESENT_HEADER)
 _PANEL = _ABI.structs["mtgs_present_panel"]
@@ -268,11 +269,14 @@ def colorize_depth(depth: Tensor, accumulation: Optional[Tensor] = None, near_pl
 
 def viewer_frame(outputs: Dict[str, Tensor], output_render: str, options: ColormapOptions = ColormapOptions(),
                  split_output_render: Optional[str] = None, split_options: Optional[ColormapOptions] = None,
-                 split_percentage: float = 0.5, client_aspect: Optional[float] = None, out: Optional[Tensor] = None) -> Tensor:
+                 split_percentage: float = 0.5, client_aspect: Optional[float] = None, out: Optional[Tensor] = None,
+                 jpeg_quality: Optional[int] = None, jpeg_out: Optional[JpegStream] = None) -> Union[Tensor, JpegStream]:
     """The uint8 frame RenderStateMachine._send_output_to_viewer hands to the client (render_state_machine.py:251-296): the
     selected output through apply_colormap; with `split_output_render` the split view (the split output from column split_index on,
     that column in SPLIT_COLOR); `(x * 255).type(torch.uint8)`; zero padding to `client_aspect` (W / H) by pad_sizes' rule.  `out`
-    (uint8 [H + 2 ph, W + 2 pw, 3]) is written in place: nothing is allocated."""
+    (uint8 [H + 2 ph, W + 2 pw, 3]) is written in place: nothing is allocated.  With `jpeg_quality` (set_background_image's
+    jpeg_quality) the frame is encoded where it lies and its JpegStream is returned instead (mtgs_amd.jpeg, 4:2:0; `jpeg_out` is
+    encoded into in place); None leaves everything as it is."""
     if output_render not in outputs:
         raise KeyError(f"output_render {output_render!r} is not among the outputs {sorted(outputs)}")
     a = _source(outputs[output_render], options, f"outputs[{output_render!r}]")
@@ -288,7 +292,8 @@ def viewer_frame(outputs: Dict[str, Tensor], output_render: str, options: Colorm
             raise ValueError(f"split_output_render {split_output_render!r} is {b.height} x {b.width}, output_render {output_render!r} {H} x {W}")
         k = split_index(split_percentage, W)
         sources, places, column = [a, b], [(ph, pw, H, k, 0), (ph, pw + k, H, W - k, k)], pw + k
-    return _compose(sources, places, H + 2 * ph, W + 2 * pw, column, _U8_TRUNCATE, out)
+    frame = _compose(sources, places, H + 2 * ph, W + 2 * pw, column, _U8_TRUNCATE, out)
+    return frame if jpeg_quality is None else encode_jpeg(frame, jpeg_quality, out=jpeg_out)
 
 
 def viewer_depth(depth: Tensor, state: str, scale_ratio: float = 1.0, out: Optional[Tensor] = None) -> Tensor:
@@ -310,10 +315,13 @@ def viewer_depth(depth: Tensor, state: str, scale_ratio: float = 1.0, out: Optio
 
 
 def render_frame(outputs: Dict[str, Tensor], rendered_output_names: Sequence[str], depth_near_plane: Optional[float] = None,
-                 depth_far_plane: Optional[float] = None, options: ColormapOptions = ColormapOptions(), out: Optional[Tensor] = None) -> Tensor:
+                 depth_far_plane: Optional[float] = None, options: ColormapOptions = ColormapOptions(), out: Optional[Tensor] = None,
+                 jpeg_quality: Optional[int] = None, jpeg_out: Optional[JpegStream] = None) -> Union[Tensor, JpegStream]:
     """The render tool's frame (tools/render.py:131-165): every named output coloured -- a name containing "depth" through
     apply_depth_colormap with outputs["accumulation"] and the given planes, the others through apply_colormap -- and concatenated
-    along the width, as uint8 [H, sum W, 3] by the rounding conversion (clip(x, 0, 1) * 255 + 0.5, truncated)."""
+    along the width, as uint8 [H, sum W, 3] by the rounding conversion (clip(x, 0, 1) * 255 + 0.5, truncated).  With
+    `jpeg_quality` (tools/render.py:729-734, media.write_image(fmt="jpeg", quality=)) the JpegStream of that frame is returned
+    instead, as from viewer_frame."""
     if len(rendered_output_names) == 0:
         raise ValueError("rendered_output_names is empty")
     if len(rendered_output_names) > MAX_PANELS:
@@ -334,4 +342,5 @@ def render_frame(outputs: Dict[str, Tensor], rendered_output_names: Sequence[str
             raise ValueError(f"outputs[{name!r}] has {s.height} rows, outputs[{rendered_output_names[0]!r}] has {H}: panels side by side need one height")
     columns = concat_columns([s.width for s in sources])
     places = [(0, x0, H, s.width, 0) for x0, s in zip(columns, sources)]
-    return _compose(sources, places, H, columns[-1] + sources[-1].width, -1, _U8_ROUND, out)
+    frame = _compose(sources, places, H, columns[-1] + sources[-1].width, -1, _U8_ROUND, out)
+    return frame if jpeg_quality is None else encode_jpeg(frame, jpeg_quality, out=jpeg_out)

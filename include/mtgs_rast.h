@@ -227,7 +227,10 @@ int mtgs_sort_pairs(int64_t M, int key_bits, int64_t *keys_in, int32_t *vals_in,
  *                      as soon as the totals are known, one kernel before the call's work ends, so a host thread
  *                      polling host_totals[1] == host_tag reads n_vis and M without synchronising the stream.
  *  mtgs_bin_scan     : cum[n_vis] i64 = inclusive sum of tiles_per_gauss[ids_sorted[r]].
- *  mtgs_bin_emit     : tile_keys[M] u32 = cam*n_tiles + tile, gids[M] i32, in depth order.
+ *  mtgs_bin_emit     : tile_keys[M] u32 = cam*n_tiles + tile, gids[M] i32, in depth order.  M = cum[n_vis-1].
+ *                      Entries of ids_sorted WITHOUT a tile are allowed (radii > 0 with the rectangle off the
+ *                      grid, tiles_per_gauss == 0): cum may have plateaus of any length, such entries emit
+ *                      nothing, and every tile_keys[i] < C*n_tiles.
  *  mtgs_sort_pairs_u32 : stable LSD sort of (u32 key, i32 value) on key bits [0, key_bits).
  *  mtgs_bin_sort_tiles : the same sort on the tile bits, with gsplat's isect_ids[M] i64 written by the
  *                      last pass directly (keys_scratch[M] u32 is a scratch buffer).

@@ -112,6 +112,50 @@ struct InclusiveSink {
 // slot, the next 2048 prefix sums go to LDS, and every slot locates its Gaussian with an 11-step
 // search in LDS (neighbouring lanes read the same words -> broadcasts).  Stores are fully coalesced.
 constexpr int EMIT_ITEMS = 8, EMIT_TILE = BIN_BLOCK * EMIT_ITEMS;
+
+// The slots of one block.  s_c: cum[r0 .. r0+EMIT_TILE) as 32-bit words (0x7fffffff behind n_vis), base0 = cum[r0-1].
+// PLATEAUS = false: every slot's Gaussian is known to be in that window.  PLATEAUS = true: a slot whose Gaussian is not
+// (s_c[EMIT_TILE-1] <= i) searches cum in global memory.
+template <bool PLATEAUS>
+__device__ __forceinline__ void emit_slots(
+    int64_t M, int64_t n_vis, const int32_t *__restrict__ ids_sorted, int64_t N, const float *__restrict__ means2d,
+    const int32_t *__restrict__ radii, const int64_t *__restrict__ cum, float ts, int tw, int th,
+    uint32_t *__restrict__ tile_keys, int32_t *__restrict__ gids, const int32_t *s_c, int64_t s0, int64_t r0, int32_t base0) {
+    const int tid = threadIdx.x;
+#pragma unroll
+    for (int e = 0; e < EMIT_ITEMS; ++e) {
+        const int64_t i = s0 + e * BIN_BLOCK + tid;
+        if (i >= M) break;
+        int l = 0, h = EMIT_TILE - 1;  // first l with s_c[l] > i; <= EMIT_TILE-1 if it exists
+        while (l < h) {
+            const int mid = (l + h) >> 1;
+            if ((int64_t)s_c[mid] <= i) l = mid + 1; else h = mid;
+        }
+        int32_t excl = l > 0 ? s_c[l - 1] : base0;
+        int64_t r = r0 + l;   // first r with cum[r] > i: it owns slot i, and cum[r] > cum[r-1], so its rectangle is not empty
+        if (PLATEAUS && (int64_t)s_c[EMIT_TILE - 1] <= i) {
+            // cum[r0+EMIT_TILE-1] <= i < M = cum[n_vis-1] (the sentinel of a short window exceeds every i): the answer
+            // lies in [r0+EMIT_TILE, n_vis-1]
+            int64_t a = r0 + EMIT_TILE, b = n_vis - 1;
+            while (a < b) {
+                const int64_t mid = (a + b) >> 1;
+                if (cum[mid] <= i) a = mid + 1; else b = mid;
+            }
+            excl = (int32_t)cum[a - 1];
+            r = a;
+        }
+        const int32_t idx = ids_sorted[r];
+        const float2 m = reinterpret_cast<const float2 *>(means2d)[idx];
+        const Rect q = tile_rect(m.x, m.y, radii[idx], ts, tw, th);
+        const int local = (int)(i - excl), bw = q.x1 - q.x0;
+        const int row = local / bw, col = local - row * bw;
+        // camera of flatten id idx: a 32-bit division (C*N < 2^31), none at all for the single camera MTGS renders
+        const uint32_t cam = (uint32_t)idx < (uint32_t)N ? 0u : (uint32_t)idx / (uint32_t)N;
+        tile_keys[i] = cam * (uint32_t)(tw * th) + (uint32_t)((q.y0 + row) * tw + q.x0 + col);
+        gids[i] = idx;
+    }
+}
+
 __global__ __launch_bounds__(BIN_BLOCK) void bin_emit_kernel(
     int64_t M, int64_t n_vis, const int32_t *__restrict__ ids_sorted, int64_t N,
     const float *__restrict__ means2d, const int32_t *__restrict__ radii, const int64_t *__restrict__ cum,
@@ -134,7 +178,6 @@ __global__ __launch_bounds__(BIN_BLOCK) void bin_emit_kernel(
         lo = last_below + 1;
     }
     const int64_t r0 = lo;
-    // every Gaussian owns >= 1 slot, so the block's slots touch at most Gaussians r0 .. r0+EMIT_TILE-1
 #pragma unroll
     for (int e = 0; e < EMIT_ITEMS; ++e) {
         const int k = e * BIN_BLOCK + tid;
@@ -142,26 +185,15 @@ __global__ __launch_bounds__(BIN_BLOCK) void bin_emit_kernel(
     }
     const int32_t base0 = r0 > 0 ? (int32_t)cum[r0 - 1] : 0;
     __syncthreads();
-#pragma unroll
-    for (int e = 0; e < EMIT_ITEMS; ++e) {
-        const int64_t i = s0 + e * BIN_BLOCK + tid;
-        if (i >= M) break;
-        int l = 0, h = EMIT_TILE - 1;  // first l with s_c[l] > i; it exists and is <= EMIT_TILE-1
-        while (l < h) {
-            const int mid = (l + h) >> 1;
-            if ((int64_t)s_c[mid] <= i) l = mid + 1; else h = mid;
-        }
-        const int32_t excl = l > 0 ? s_c[l - 1] : base0;
-        const int32_t idx = ids_sorted[r0 + l];
-        const float2 m = reinterpret_cast<const float2 *>(means2d)[idx];
-        const Rect q = tile_rect(m.x, m.y, radii[idx], ts, tw, th);
-        const int local = (int)(i - excl), bw = q.x1 - q.x0;
-        const int row = local / bw, col = local - row * bw;
-        // camera of flatten id idx: a 32-bit division (C*N < 2^31), none at all for the single camera MTGS renders
-        const uint32_t cam = (uint32_t)idx < (uint32_t)N ? 0u : (uint32_t)idx / (uint32_t)N;
-        tile_keys[i] = cam * (uint32_t)(tw * th) + (uint32_t)((q.y0 + row) * tw + q.x0 + col);
-        gids[i] = idx;
-    }
+    // When every Gaussian owns >= 1 slot (projected input: project_fwd_body.hpp), the block's slots touch at most
+    // Gaussians r0 .. r0+EMIT_TILE-1, the LDS window.  Entries WITHOUT a tile (radii > 0, rectangle off the grid: the
+    // public isect_tiles accepts them) make cum plateau; a slot behind EMIT_TILE or more of them is not in the window.
+    // Whether the block has such a slot shows at its LAST slot (block-uniform; never on projected input).
+    const int64_t last_slot = min(M, s0 + EMIT_TILE) - 1;
+    if ((int64_t)s_c[EMIT_TILE - 1] > last_slot)
+        emit_slots<false>(M, n_vis, ids_sorted, N, means2d, radii, cum, ts, tw, th, tile_keys, gids, s_c, s0, r0, base0);
+    else
+        emit_slots<true>(M, n_vis, ids_sorted, N, means2d, radii, cum, ts, tw, th, tile_keys, gids, s_c, s0, r0, base0);
 }
 
 // last-pass epilogue of the tile sort: (tile key, Gaussian index) -> gsplat's 64-bit isect_id

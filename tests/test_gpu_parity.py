@@ -117,27 +117,41 @@ def test_sort_is_stable_on_masked_bits(gs, oracle):
     assert np.array_equal(ko.cpu().numpy(), r_k) and np.array_equal(vo.cpu().numpy(), r_v)
 
 
-@pytest.mark.parametrize("M", [1, 63, 1025, 5000, 300_000, 1 << 20, (1 << 20) + 1, 3_000_001])
-@pytest.mark.parametrize("key_bits", [1, 7, 12, 23, 32, 33, 46, 64])
-def test_sort_pairs_all_digit_plans(gs, M, key_bits):
-    """mtgs_sort_pairs against torch's stable sort of the masked keys: up to 2^20 keys take 1024-key tiles, larger sorts
-    4096-key tiles; every (size class, pass count, last-digit width) combination must be stable and must ignore the
-    bits above key_bits."""
+SORT_PLANS = ([pytest.param("i64", M, key_bits, id=f"{key_bits}-{M}") for key_bits in [1, 7, 12, 23, 32, 33, 46, 64]
+               for M in [1, 63, 1025, 5000, 300_000, 1 << 20, (1 << 20) + 1, 3_000_001]]
+              # the 32-bit instantiation (the tile sort of csrc/bin.hip): 1024-key tiles up to 2^20 keys and 4096-key tiles above,
+              # 1 to 4 passes, last digits of 1 to 8 bits
+              + [pytest.param("u32", M, key_bits, id=f"u32-{key_bits}-{M}") for key_bits in [1, 7, 8, 9, 13, 16, 17, 32]
+                 for M in [1, 63, 1025, 1 << 20, (1 << 20) + 1]])
+
+
+@pytest.mark.parametrize("ktype,M,key_bits", SORT_PLANS)
+def test_sort_pairs_all_digit_plans(gs, ktype, M, key_bits):
+    """mtgs_sort_pairs (and mtgs_sort_pairs_u32) against torch's stable sort of the masked keys: up to 2^20 keys take 1024-key
+    tiles, larger sorts 4096-key tiles; every (size class, pass count, last-digit width) combination must be stable and must
+    ignore the bits above key_bits."""
     from mtgs_amd._lib import call, ptr
     g = torch.Generator(device="cuda").manual_seed(M * 131 + key_bits)
     keys = torch.randint(-(1 << 62), 1 << 62, (M,), generator=g, dtype=torch.int64, device="cuda")
     if key_bits >= 12:   # ties in the low bits too: a few distinct values only
         keys = torch.where(torch.rand(M, device="cuda", generator=g) < 0.3, keys & 0x7, keys)
     vals = torch.arange(M, dtype=torch.int32, device="cuda")
+    if ktype == "u32":   # the low words of the same keys (every bit pattern, the top bit included)
+        wide = keys & 0xFFFFFFFF
+        keys = torch.where(wide >= (1 << 31), wide - (1 << 32), wide).to(torch.int32)
+        assert bool((keys.long() & 0xFFFFFFFF == wide).all()) and (M < 1000 or bool((keys < 0).any()))
     ko, vo = torch.empty_like(keys), torch.empty_like(vals)
     ws = C.c_size_t(0)
-    call("mtgs_sort_workspace_bytes", M, C.byref(ws))
+    call("mtgs_sort_workspace_bytes" if ktype == "i64" else "mtgs_sort_u32_workspace_bytes", M, C.byref(ws))
     w = torch.empty(ws.value, dtype=torch.uint8, device="cuda")
-    call("mtgs_sort_pairs", M, key_bits, ptr(keys), ptr(vals), ptr(ko), ptr(vo), ptr(w), ws.value,
-         torch.cuda.current_stream().cuda_stream)
-    masked = keys if key_bits == 64 else keys & ((1 << key_bits) - 1)
-    if key_bits == 64:    # unsigned order of the 64-bit pattern
-        masked = keys ^ (-(1 << 63))
+    call("mtgs_sort_pairs" if ktype == "i64" else "mtgs_sort_pairs_u32", M, key_bits, ptr(keys), ptr(vals), ptr(ko), ptr(vo), ptr(w),
+         ws.value, torch.cuda.current_stream().cuda_stream)
+    if ktype == "u32":
+        masked = (keys.long() & 0xFFFFFFFF) & ((1 << key_bits) - 1)
+    else:
+        masked = keys if key_bits == 64 else keys & ((1 << key_bits) - 1)
+        if key_bits == 64:    # unsigned order of the 64-bit pattern
+            masked = keys ^ (-(1 << 63))
     order = torch.sort(masked, stable=True).indices
     assert torch.equal(vo.long(), order)
     assert torch.equal(ko, keys[order])

@@ -20,9 +20,10 @@ __device__ __forceinline__ float block_sum4(float v, float *lds) {
     return (lds[0] + lds[1]) + (lds[2] + lds[3]);
 }
 
-// Fixed-order fp64 sum over a block of BLOCK threads (a halving tree in `lds`, BLOCK doubles); returns the total.
-template <int BLOCK>
-__device__ __forceinline__ double block_tree_sum_f64(double a, double *lds) {
+// Fixed-order sum over a block of BLOCK threads (a halving tree in `lds`, BLOCK elements); returns the total.  `lds` may be reused
+// once every thread has passed a barrier behind the call.  Callers name the precision: block_tree_sum_f64 / _f32.
+template <int BLOCK, class T>
+__device__ __forceinline__ T block_tree_sum(T a, T *lds) {
     const int tid = threadIdx.x;
     lds[tid] = a;
     __syncthreads();
@@ -32,6 +33,10 @@ __device__ __forceinline__ double block_tree_sum_f64(double a, double *lds) {
     }
     return lds[0];
 }
+template <int BLOCK>
+__device__ __forceinline__ double block_tree_sum_f64(double a, double *lds) { return block_tree_sum<BLOCK>(a, lds); }
+template <int BLOCK>
+__device__ __forceinline__ float block_tree_sum_f32(float a, float *lds) { return block_tree_sum<BLOCK>(a, lds); }
 
 // Fixed-order fp64 sum of K interleaved float partials over nblocks blocks, by one block of BLOCK threads; thread 0 ends
 // with the totals.  (One tree for all K columns: one barrier per level, not K.)

@@ -62,6 +62,13 @@ __device__ __forceinline__ int wave_max_i32(int v) {
     for (int o = 32; o > 0; o >>= 1) v = max(v, __shfl_xor(v, o, 64));
     return v;
 }
+// Sum over the wave by an xor butterfly (float or int): every lane receives the same total.
+template <class T>
+__device__ __forceinline__ T wave_sum_all(T v) {
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
+    return v;
+}
 __device__ __forceinline__ int lane_id() { return (int)(threadIdx.x & 63); }
 // torch.abs's backward: grad * sgn(x) with sgn(0) = sgn(NaN) = 0
 __device__ __forceinline__ float sgn0(float d) { return d > 0.f ? 1.f : (d < 0.f ? -1.f : 0.f); }

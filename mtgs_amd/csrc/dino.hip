@@ -10,37 +10,30 @@
 //   dino_patch_weights  one workgroup of 16 waves, the NEAREST tables in LDS: per patch the count of non-zero mask pixels behind its 196
 //                       window pixels, four patches per wave in flight; counts are integers, so the weights and their sum do not
 //                       depend on an order.
-//   dino_gemm           lpips_conv's tile: 256 threads = 4 waves, output tile 128 (M) x 64 (N) (128 x 32 where that tile would make fewer
-//                       than 512 workgroups: N = 768 at 2740 rows is 264 of them on 256 CUs), K in steps of 32 through LDS, the next
-//                       step's operands fetched into registers before the current one is multiplied; wave w owns rows 32w .. 32w + 31
-//                       and both 32-column halves.  Lane l = (i = l & 31, h = l >> 5) supplies A(i, 2s + h) and B(2s + h, i) to
-//                       k-step s; register v of the result is row (v & 3) + 8 (v >> 2) + 4h, column i.  K is never split over lanes, waves
-//                       or workgroups; one lane's fma chain runs in k order and is RESTARTED every 128 k's, the finished partial sum
-//                       added to a running total in k order (K <= 128 is one chain): a single chain over K = 3072 measured 7.5e-6 on
-//                       768-wide features against 2.5e-6 of the fp32 CPU restatement, outside the bound of tests/test_gpu_dino.py.
-//                       The last step is zero-filled beyond K (K = 588).  Epilogues: bias | bias, GELU | bias, gamma, + residual in place |
+//   dino_gemm           the tile of mfma_f32_tile.hpp, 128 (M) x 64 (N) per workgroup (128 x 32 where that tile would make fewer than
+//                       512 workgroups: N = 768 at 2740 rows is 264 of them on 256 CUs).  One lane's fma chain is RESTARTED every
+//                       128 k's (K <= 128 is one chain): a single chain over K = 3072 measured 7.5e-6 on 768-wide features against
+//                       2.5e-6 of the fp32 CPU restatement, outside the bound of tests/test_gpu_dino.py.  The last step is
+//                       zero-filled beyond K (K = 588).  Epilogues: bias | bias, GELU | bias, gamma, + residual in place |
 //                       bias + pos_embed with the row-to-token remap (and the two class rows).
 //   dino_layernorm      one wave per row held in registers; the mean, then the variance about the mean, by wave_reduce_x4.
 //   dino_attention      one workgroup per (image, head, 128 query rows), a wave per 32 of them; K and V blocks of 32 keys through
 //                       LDS (shared by the four waves, the next block prefetched into registers); S = (q / 8) k^T by 32 MFMAs, through a
 //                       per-wave LDS tile into "one lane per (row, half of the keys)" for the running maximum and the exponentials,
-//                       P back through the same tile as the A operand of P V (32 MFMAs into two accumulators).
+//                       P back through the same tile as the A operand of P V (the tile's k-steps, 32 MFMAs into two accumulators).
 //   dino_cosine         one wave per patch: both rows in registers, two norms, the sum of the normalised products, x the weight.
 //   dino_finish         one workgroup: the per-patch terms in a fixed tree, / the weight sum, or 0 when that is <= 1e-6.
 #include <math.h>
 
+#include "block_reduce.hpp"
 #include "common.hpp"
+#include "mfma_f32_tile.hpp"
 #include "wave_reduce.hpp"
 
 namespace {
 
-constexpr int TB = 256;
-constexpr int BM = 128, BN = 64, BK = 32, SA = BK + 1;
-constexpr int KQ = BK / 4;                 // 16-byte pieces of one row of the A tile
-constexpr int RA = BM * KQ / TB;           // rows of the A tile per thread
 constexpr int WIDE_GRID = 512;             // workgroups of 128 x 64 from which on that tile is used (two per CU); below: 128 x 32
 constexpr int SEG = 128;                   // k's per fma chain of the GEMM
-static_assert(BM * KQ % TB == 0 && BM == 32 * (TB / 64) && BN == 64 && SEG % BK == 0, "tile shape and loaders");
 constexpr int PATCH = MTGS_DINO_PATCH, PP = PATCH * PATCH, PK = 3 * PP;       // 14, 196, 588
 constexpr int HD = MTGS_DINO_HEAD_DIM;
 constexpr int LN_Q = MTGS_DINO_MAX_DIM / 64;      // elements of a row per lane
@@ -50,9 +43,6 @@ constexpr int PW_TB = 1024, PW_U = 4;
 constexpr int MAX_S = 4096;                    // the largest network input side
 constexpr int64_t LIMIT = (int64_t)1 << 31;
 
-typedef float f32x16 __attribute__((ext_vector_type(16)));
-
-__device__ __forceinline__ int acc_row(int v, int h) { return (v & 3) + 8 * (v >> 2) + 4 * h; }
 __device__ __forceinline__ int clampi(int v, int lo, int hi) { return v < lo ? lo : (v > hi ? hi : v); }
 
 // every lane receives the sum over the wave, in one fixed order
@@ -142,9 +132,7 @@ __global__ __launch_bounds__(PW_TB) void dino_patch_weights_kernel(int H, int W,
         }
 #pragma unroll
         for (int u = 0; u < PW_U; ++u) {
-            int c = cnt[u];
-#pragma unroll
-            for (int o = 32; o > 0; o >>= 1) c += __shfl_xor(c, o, 64);
+            const int c = wave_sum_all(cnt[u]);
             const int p = p0 + u * (PW_TB / 64);
             if (l == 0 && p < G2) weights[p] = (float)c / (float)PP;
             total += c;
@@ -176,26 +164,11 @@ __device__ __forceinline__ float gelu_erf(float x) { return 0.5f * x * (1.f + er
 // NH: 32-column halves of the output tile per workgroup (2: 128 x 64, 1: 128 x 32 for grids that would leave CUs idle)
 template <bool VEC, int NH>
 __global__ __launch_bounds__(TB, 4) void dino_gemm_kernel(Gemm c) {      // four workgroups per CU: at most 128 registers
-    __shared__ float sA[BM * SA];
-    constexpr int SB = 32 * NH, BQ = SB / 4, BR = TB / BQ, RB = BK / BR;      // B tile: row stride, float4 per row, rows per pass, passes
-    __shared__ __attribute__((aligned(16))) float sB[BK * SB];
-    const int t = threadIdx.x, wv = t >> 6, l = t & 63, i = l & 31, hh = l >> 5;
-    const int m0 = blockIdx.x * BM, n0 = blockIdx.y * SB;
-
-    const int kq = t % KQ, ar = t / KQ;            // A: k = k0 + 4 kq .. + 3 of the rows ar + (TB / KQ) r
-    const int kb = t / BQ, nq = t % BQ;            // B: rows kb + BR r of the K-step, columns n0 + 4 nq .. + 3 (N is a multiple of 64)
-    float4 ra[RA], rb[RB];
-    auto fetch = [&](int k0) {
-#pragma unroll
-        for (int r = 0; r < RB; ++r) {
-            const int k = k0 + kb + BR * r;
-            rb[r] = make_float4(0.f, 0.f, 0.f, 0.f);
-            if (k < c.K) rb[r] = *reinterpret_cast<const float4 *>(c.w + (size_t)k * c.N + n0 + 4 * nq);
-        }
-        const int k = k0 + 4 * kq;                 // K is a multiple of 4: the four elements stand or fall together
+    auto fetch_a = [&](int k0, float4 (&ra)[RA]) {
+        const int k = k0 + 4 * tile_a_kq();        // K is a multiple of 4: the four elements stand or fall together
 #pragma unroll
         for (int r = 0; r < RA; ++r) {
-            const int m = m0 + ar + (TB / KQ) * r;
+            const int m = blockIdx.x * BM + tile_a_row(r);
             ra[r] = make_float4(0.f, 0.f, 0.f, 0.f);
             if (m < c.M && k < c.K) {
                 const float *p = c.a + (size_t)m * c.K + k;
@@ -204,60 +177,12 @@ __global__ __launch_bounds__(TB, 4) void dino_gemm_kernel(Gemm c) {      // four
             }
         }
     };
-    auto stage = [&]() {
-#pragma unroll
-        for (int r = 0; r < RA; ++r) {
-            float *d = sA + (ar + (TB / KQ) * r) * SA + 4 * kq;
-            d[0] = ra[r].x; d[1] = ra[r].y; d[2] = ra[r].z; d[3] = ra[r].w;
-        }
-#pragma unroll
-        for (int r = 0; r < RB; ++r) *reinterpret_cast<float4 *>(sB + (kb + BR * r) * SB + 4 * nq) = rb[r];
-    };
-
-    f32x16 acc0, acc1, tot0, tot1;             // the running chain and the total of the finished ones
-#pragma unroll
-    for (int v = 0; v < 16; ++v) { acc0[v] = 0.f; acc1[v] = 0.f; tot0[v] = 0.f; tot1[v] = 0.f; }
-
-    fetch(0);
-    stage();
-    __syncthreads();
-    for (int k0 = 0; k0 < c.K; k0 += BK) {
-        const bool more = k0 + BK < c.K;
-        if (more) fetch(k0 + BK);
-        if (k0 != 0 && k0 % SEG == 0) {
-#pragma unroll
-            for (int v = 0; v < 16; ++v) { tot0[v] += acc0[v]; tot1[v] += acc1[v]; acc0[v] = 0.f; acc1[v] = 0.f; }
-        }
-        const float *pa = sA + (wv * 32 + i) * SA + hh;
-        const float *pb = sB + hh * SB + i;
-#pragma unroll
-        for (int s = 0; s < BK / 2; ++s) {
-            const float a = pa[2 * s];
-            acc0 = __builtin_amdgcn_mfma_f32_32x32x2f32(a, pb[2 * s * SB], acc0, 0, 0, 0);
-            if (NH == 2) acc1 = __builtin_amdgcn_mfma_f32_32x32x2f32(a, pb[2 * s * SB + 32], acc1, 0, 0, 0);
-        }
-        __syncthreads();
-        if (more) {
-            stage();
-            __syncthreads();
-        }
-    }
-
-#pragma unroll
-    for (int v = 0; v < 16; ++v) { acc0[v] += tot0[v]; acc1[v] += tot1[v]; }      // + 0 for K <= SEG: the single chain's bits
-
-    // epilogue: lane i holds column i of both halves, 128-byte rows of stores
-    const int G2 = c.tokens - 1;
-#pragma unroll
-    for (int half = 0; half < NH; ++half) {
-        const int n = n0 + 32 * half + i;
+    const int G2 = c.tokens - 1;                   // the column's bias and gamma are read once, then the epilogue of every row
+    mfma_f32_tile<NH, SEG, false>(c.w, c.M, c.N, c.K, fetch_a, [&](int n) {
         const float b = c.bias[n];
         const float g = c.epi == MTGS_DINO_EPI_SCALE_RESIDUAL ? c.gamma[n] : 0.f;
-#pragma unroll
-        for (int v = 0; v < 16; ++v) {
-            const int m = m0 + wv * 32 + acc_row(v, hh);
-            if (m >= c.M) continue;
-            const float x = (half ? acc1[v] : acc0[v]) + b;
+        return [&c, G2, n, b, g](int m, float sum) {
+            const float x = sum + b;
             if (c.epi == MTGS_DINO_EPI_BIAS) {
                 c.out[(size_t)m * c.N + n] = x;
             } else if (c.epi == MTGS_DINO_EPI_BIAS_GELU) {
@@ -269,10 +194,11 @@ __global__ __launch_bounds__(TB, 4) void dino_gemm_kernel(Gemm c) {      // four
                 const int im = m / G2, p = m - im * G2;
                 c.out[((size_t)im * c.tokens + 1 + p) * c.N + n] = x + c.pos[(size_t)(1 + p) * c.N + n];
             }
-        }
-    }
-    if (c.epi == MTGS_DINO_EPI_PATCH_EMBED && blockIdx.x == 0 && t < SB) {        // the two class rows, this block's columns
-        const int n = n0 + t;
+        };
+    });
+    const int t = threadIdx.x;
+    if (c.epi == MTGS_DINO_EPI_PATCH_EMBED && blockIdx.x == 0 && t < 32 * NH) {   // the two class rows, this block's columns
+        const int n = blockIdx.y * 32 * NH + t;
         const float v = c.cls[n] + c.pos[n];
         c.out[n] = v;
         c.out[(size_t)c.tokens * c.N + n] = v;
@@ -397,14 +323,7 @@ __global__ __launch_bounds__(TB) void dino_attention_kernel(int T, int heads, co
             o0[v] *= al;
             o1[v] *= al;
         }
-        const float *pp = S + i * SSS + hh;
-        const float *pv = sV + hh * HD + i;
-#pragma unroll
-        for (int s = 0; s < AKB / 2; ++s) {
-            const float a = pp[2 * s], b0 = pv[2 * s * HD], b1 = pv[2 * s * HD + 32];
-            o0 = __builtin_amdgcn_mfma_f32_32x32x2f32(a, b0, o0, 0, 0, 0);
-            o1 = __builtin_amdgcn_mfma_f32_32x32x2f32(a, b1, o1, 0, 0, 0);
-        }
+        mfma_f32_ksteps<2, HD, AKB / 2>(S + i * SSS, sV, o0, o1);
         __syncthreads();
         if (more) {
             stage();
@@ -453,15 +372,10 @@ __global__ __launch_bounds__(TB) void dino_finish_kernel(int G2, const float *__
     const int t = threadIdx.x;
     float v = 0.f;
     for (int p = t; p < G2; p += TB) v += terms[p];
-    s[t] = v;
-    __syncthreads();
-    for (int o = TB / 2; o > 0; o >>= 1) {
-        if (t < o) s[t] += s[t + o];
-        __syncthreads();
-    }
+    const float sum = block_tree_sum_f32<TB>(v, s);
     if (t == 0) {
         const float total = weights[G2];
-        out[0] = total > 1e-6f ? s[0] / total : 0.f;
+        out[0] = total > 1e-6f ? sum / total : 0.f;
     }
 }
 

@@ -2,12 +2,8 @@
 // MFMA (v_mfma_f32_32x32x2_f32), two max-pools, and a fused tail (channel norms, weighted squared difference, spatial mean).
 //
 // Activations are NHWC, both images in one array [2, h, w, C], so a layer is ONE launch with M = 2 * oh * ow rows.
-//   lpips_conv      block 256 threads = 4 waves, output tile 128 (M) x 64 (N), K in steps of 32 through LDS; wave w owns rows
-//                   32w .. 32w + 31 and both 32-column halves (two independent accumulators).  The next K-step's operands are
-//                   fetched into registers before the current one is multiplied.  A: sA[m][k] (stride 33: the 32 rows a k-step reads
-//                   fall into 32 banks), B: sB[k][n].  Lane l = (i = l & 31, h = l >> 5) supplies A(i, 2s + h) and B(2s + h, i) to
-//                   k-step s; register v of the result is row (v & 3) + 8 (v >> 2) + 4h, column i.  K is never split: every output
-//                   is one k-ordered fma chain, the last k-step zero-filled beyond K (K = 363 for layer 1).
+//   lpips_conv      the tile of mfma_f32_tile.hpp, 128 (M) x 64 (N) per workgroup, the chain never restarted; cout is a multiple of 32
+//                   only, so the last column tile may be half empty.  The last k-step is zero-filled beyond K (K = 363 for layer 1).
 //                   Three loaders for A: VEC (cin % 32 == 0: a K-step lies inside one tap, 16-byte loads), SCALAR (any cin), FIRST
 //                   (the two [H, W, 3] images and the mask, input transform applied on load; padding taps stay 0).
 //   lpips_maxpool   3x3 stride 2, four channels per thread.
@@ -17,21 +13,15 @@
 //   lpips_finish    one workgroup: the partials of each layer in a fixed tree, / pixel count, summed layer by layer.
 #include <math.h>
 
+#include "block_reduce.hpp"
 #include "common.hpp"
+#include "mfma_f32_tile.hpp"
 
 namespace {
 
-constexpr int TB = 256;
-constexpr int BM = 128, BN = 64, BK = 32, SA = BK + 1, SB = BN;
-constexpr int KQ = BK / 4;                 // 16-byte pieces of one row of the A tile
-constexpr int RA = BM * KQ / TB;           // rows of the A tile per thread
-constexpr int RB = BK * (BN / 4) / TB;     // rows of the B tile per thread
-static_assert(BM * KQ % TB == 0 && BK * (BN / 4) % TB == 0 && BM == 32 * (TB / 64) && BN == 64, "tile shape and loaders");
 constexpr int DIST_BLOCKS = 256;          // partials per layer
 constexpr int DIST_MAX_Q = 8;             // channels per lane held in registers: cout <= 512
 constexpr int N_LAYERS = 5;
-
-typedef float f32x16 __attribute__((ext_vector_type(16)));
 
 enum { LOAD_VEC = 0, LOAD_SCALAR = 1, LOAD_FIRST = 2 };
 
@@ -45,8 +35,6 @@ struct Conv {
     int n, h, w, cin, cout, kh, kw, stride, pad, oh, ow, M, K, relu, normalize;     // n images: M = n * oh * ow
 };
 
-__device__ __forceinline__ int acc_row(int v, int h) { return (v & 3) + 8 * (v >> 2) + 4 * h; }
-
 __device__ __forceinline__ float first_value(const Conv &c, const float *img, int iy, int ix, int ch) {
     const float shift = ch == 0 ? -.030f : (ch == 1 ? -.088f : -.188f);
     const float scale = ch == 0 ? .458f : (ch == 1 ? .449f : .450f);
@@ -59,18 +47,12 @@ __device__ __forceinline__ float first_value(const Conv &c, const float *img, in
 
 template <int MODE>
 __global__ __launch_bounds__(TB) void lpips_conv_kernel(Conv c) {
-    __shared__ float sA[BM * SA];
-    __shared__ __attribute__((aligned(16))) float sB[BK * SB];
-    const int t = threadIdx.x, wv = t >> 6, l = t & 63, i = l & 31, hh = l >> 5;
-    const int m0 = blockIdx.x * BM, n0 = blockIdx.y * BN;
-
-    // A loader: this thread fetches k = k0 + 4 kq .. + 3 of the rows ar + (TB / KQ) r
-    const int kq = t % KQ, ar = t / KQ;
+    const int kq = tile_a_kq();            // A loader: the window origin of this thread's rows, then one of three fetches
     int oy0[RA], ox0[RA], img[RA];
     bool rowok[RA];
 #pragma unroll
     for (int r = 0; r < RA; ++r) {
-        const int m = m0 + ar + (TB / KQ) * r;
+        const int m = blockIdx.x * BM + tile_a_row(r);
         rowok[r] = m < c.M;
         const int mm = rowok[r] ? m : 0;
         const int per = c.oh * c.ow;
@@ -80,18 +62,7 @@ __global__ __launch_bounds__(TB) void lpips_conv_kernel(Conv c) {
         oy0[r] = oy * c.stride - c.pad;
         ox0[r] = (q - oy * c.ow) * c.stride - c.pad;
     }
-    // B loader: rows kb + 16 r of the K-step, columns n0 + 4 nq .. + 3
-    const int kb = t >> 4, nq = t & 15;
-    const bool colok = n0 + 4 * nq < c.cout;      // cout is a multiple of 32, so the four columns stand or fall together
-
-    float4 ra[RA], rb[RB];
-    auto fetch = [&](int k0) {
-#pragma unroll
-        for (int r = 0; r < RB; ++r) {
-            const int k = k0 + kb + 16 * r;
-            rb[r] = make_float4(0.f, 0.f, 0.f, 0.f);
-            if (colok && k < c.K) rb[r] = *reinterpret_cast<const float4 *>(c.wt + (size_t)k * c.cout + n0 + 4 * nq);
-        }
+    auto fetch_a = [&](int k0, float4 (&ra)[RA]) {
         if (MODE == LOAD_VEC) {
             const int tap = k0 / c.cin, ch = k0 - tap * c.cin + 4 * kq;
             const int ky = tap / c.kw, kx = tap - ky * c.kw;
@@ -124,56 +95,15 @@ __global__ __launch_bounds__(TB) void lpips_conv_kernel(Conv c) {
             for (int r = 0; r < RA; ++r) ra[r] = make_float4(va[r][0], va[r][1], va[r][2], va[r][3]);
         }
     };
-    auto stage = [&]() {
-#pragma unroll
-        for (int r = 0; r < RA; ++r) {
-            float *d = sA + (ar + (TB / KQ) * r) * SA + 4 * kq;
-            d[0] = ra[r].x; d[1] = ra[r].y; d[2] = ra[r].z; d[3] = ra[r].w;
-        }
-#pragma unroll
-        for (int r = 0; r < RB; ++r) *reinterpret_cast<float4 *>(sB + (kb + 16 * r) * SB + 4 * nq) = rb[r];
-    };
-
-    f32x16 acc0, acc1;
-#pragma unroll
-    for (int v = 0; v < 16; ++v) { acc0[v] = 0.f; acc1[v] = 0.f; }
-
-    fetch(0);
-    stage();
-    __syncthreads();
-    for (int k0 = 0; k0 < c.K; k0 += BK) {
-        const bool more = k0 + BK < c.K;
-        if (more) fetch(k0 + BK);
-        const float *pa = sA + (wv * 32 + i) * SA + hh;
-        const float *pb = sB + hh * SB + i;
-#pragma unroll
-        for (int s = 0; s < BK / 2; ++s) {
-            const float a = pa[2 * s], b0 = pb[2 * s * SB], b1 = pb[2 * s * SB + 32];
-            acc0 = __builtin_amdgcn_mfma_f32_32x32x2f32(a, b0, acc0, 0, 0, 0);
-            acc1 = __builtin_amdgcn_mfma_f32_32x32x2f32(a, b1, acc1, 0, 0, 0);
-        }
-        __syncthreads();
-        if (more) {
-            stage();
-            __syncthreads();
-        }
-    }
-
-    // epilogue: + bias, ReLU; lane i holds column i of both halves, 128-byte rows of stores
-#pragma unroll
-    for (int half = 0; half < 2; ++half) {
-        const int n = n0 + 32 * half + i;
-        if (n >= c.cout) continue;
+    // + bias, ReLU
+    mfma_f32_tile<2, 0, true>(c.wt, c.M, c.cout, c.K, fetch_a, [&](int n) {
         const float b = c.bias[n];
-#pragma unroll
-        for (int v = 0; v < 16; ++v) {
-            const int m = m0 + wv * 32 + acc_row(v, hh);
-            if (m >= c.M) continue;
-            float x = (half ? acc1[v] : acc0[v]) + b;
+        return [&c, n, b](int m, float x) {
+            x += b;
             if (c.relu) x = x > 0.f ? x : 0.f;
             c.out[(size_t)m * c.cout + n] = x;
-        }
-    }
+        };
+    });
 }
 
 __global__ __launch_bounds__(TB) void lpips_repack_kernel(int cout, int cin, int kh, int kw, const float *__restrict__ w,
@@ -204,12 +134,6 @@ __global__ __launch_bounds__(TB) void lpips_maxpool_kernel(int h, int w, int c4,
             m.x = v.x > m.x ? v.x : m.x; m.y = v.y > m.y ? v.y : m.y; m.z = v.z > m.z ? v.z : m.z; m.w = v.w > m.w ? v.w : m.w;
         }
     out[e] = m;
-}
-
-__device__ __forceinline__ float wave_sum_all(float v) {
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
-    return v;
 }
 
 // feat [2, P, C]; partials[blockIdx.x] = sum over this workgroup's pixels of sum_c lin[c] (u0 - u1)^2
@@ -262,13 +186,8 @@ __global__ __launch_bounds__(DIST_BLOCKS) void lpips_finish_kernel(Finish f, con
     const int t = threadIdx.x;
     float total = 0.f;
     for (int layer = 0; layer < N_LAYERS; ++layer) {
-        s[t] = t < f.blocks[layer] ? partials[layer * DIST_BLOCKS + t] : 0.f;
-        __syncthreads();
-        for (int o = DIST_BLOCKS / 2; o > 0; o >>= 1) {
-            if (t < o) s[t] += s[t + o];
-            __syncthreads();
-        }
-        if (t == 0) total += s[0] / (float)f.pixels[layer];
+        const float sum = block_tree_sum_f32<DIST_BLOCKS>(t < f.blocks[layer] ? partials[layer * DIST_BLOCKS + t] : 0.f, s);
+        if (t == 0) total += sum / (float)f.pixels[layer];
         __syncthreads();
     }
     if (t == 0) out[0] = total;

@@ -76,8 +76,9 @@ MS = (32, 33, 34, 74, 130)
 
 
 @pytest.mark.parametrize("epilogue", ["bias", "gelu", "scale_residual", "patch_embed"])
-@pytest.mark.parametrize("K,N", [(588, 128), (128, 384), (512, 128), (3072, 768)])
+@pytest.mark.parametrize("K,N", [(588, 128), (128, 384), (512, 128), (3072, 768), (4, 64), (132, 64)])
 def test_linear_every_epilogue(K, N, epilogue):
+    """K = 4 is less than one K-step; K = 132 is the smallest K past one 128-k chain, and no multiple of 32."""
     from mtgs_amd.dino import dino_linear
     g = torch.Generator().manual_seed(K + N)
     w = torch.randn(K, N, generator=g) / K ** 0.5

@@ -72,6 +72,20 @@ def test_conv_alone(layer, n, h, w):
     _assert_conv(got, _nchw64(x), *convs[layer], stride, pad, f"conv{layer + 1} on {n} x {h} x {w}")
 
 
+@pytest.mark.parametrize("cin", [8, 32])
+@pytest.mark.parametrize("cout", [32, 96])
+def test_conv_with_a_half_empty_last_column_tile(cout, cin):
+    """cout is a multiple of 32 only: the last 64-column tile holds 32 columns, which no AlexNet layer reaches (every cout there is a
+    multiple of 64).  cin = 8 takes the scalar loader (K = 72: the last K-step is partly zero-filled), cin = 32 the vector loader."""
+    from mtgs_amd.lpips import conv2d_nhwc, repack_conv_weight
+    g = torch.Generator().manual_seed(1000 * cout + cin)
+    w, b = torch.randn(cout, cin, 3, 3, generator=g) / (9 * cin) ** 0.5, 0.1 * torch.randn(cout, generator=g)
+    x = torch.randn(1, 3, 5, cin, generator=g)
+    got = conv2d_nhwc(x.cuda(), repack_conv_weight(w).cuda(), b.cuda(), 3, 1, 1)
+    assert got.shape == (1, 3, 5, cout)
+    _assert_conv(got, _nchw64(x), w, b, 1, 1, f"3x3 conv {cin} -> {cout} on 1 x 3 x 5")
+
+
 def test_conv_without_relu_and_misaligned_input():
     """relu=False keeps the negative outputs; an input that is not 16-byte aligned takes the scalar loader and gives the same bits"""
     from mtgs_amd.lpips import conv2d_nhwc

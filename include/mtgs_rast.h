@@ -39,6 +39,7 @@
 #include "mtgs_lpips.h"   /* a block of its own: the LPIPS metric (AlexNet): f32 MFMA convolutions, max-pools and the fused tail */
 #include "mtgs_dino.h"   /* a block of its own: the DINOv2 similarity metric: Pillow's resample, a ViT forward on f32 MFMA, the cosine tail */
 #include "mtgs_jpeg.h"   /* a block of its own: presented frames as baseline JPEG, byte for byte libjpeg's integer path */
+#include "mtgs_lidar.h"   /* a block of its own: lidar sweeps through the cameras: the sparse depth image, the cloud's colours and labels */
 
 #ifdef __cplusplus
 extern "C" {

@@ -46,6 +46,9 @@ DINO_EXPORTS = list(_DINO_PROTOTYPES)
 JPEG_HEADER = "mtgs_jpeg.h"                             # a seventh group, with a record of its own (mtgs_amd.jpeg)
 _JPEG_PROTOTYPES = _abi.header_abi(JPEG_HEADER).prototypes
 JPEG_EXPORTS = list(_JPEG_PROTOTYPES)
+LIDAR_HEADER = "mtgs_lidar.h"                           # an eighth group, with a record of its own (mtgs_amd.lidar)
+_LIDAR_PROTOTYPES = _abi.header_abi(LIDAR_HEADER).prototypes
+LIDAR_EXPORTS = list(_LIDAR_PROTOTYPES)
 ABI_VERSION = _abi.constant("MTGS_RAST_ABI_VERSION")
 HOT_ABI_VERSION = _abi.constant("MTGS_RAST_HOT_ABI_VERSION")      # hot-path subset: what profiles/rNN_pmc_step.json is keyed on
 
@@ -63,7 +66,7 @@ def load() -> C.CDLL:
             "mtgs_amd has no CPU or PyTorch fallback for the rasterizer.")
     lib = C.CDLL(str(LIB_PATH))
     for name, (restype, argtypes) in {**_PROTOTYPES, **_EXTENSION_PROTOTYPES, **_REFINE_SCENE_PROTOTYPES, **_PRESENT_PROTOTYPES,
-                                      **_LPIPS_PROTOTYPES, **_DINO_PROTOTYPES, **_JPEG_PROTOTYPES}.items():
+                                      **_LPIPS_PROTOTYPES, **_DINO_PROTOTYPES, **_JPEG_PROTOTYPES, **_LIDAR_PROTOTYPES}.items():
         fn = getattr(lib, name)
         fn.argtypes = argtypes
         fn.restype = restype

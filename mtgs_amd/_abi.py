@@ -4,7 +4,7 @@
     signatures()        {name: (result letter, argument letters)}: the same, as tests/golden/abi_signatures.txt spells it
     struct_dtype(name)  numpy record dtype of `typedef struct name { ... } name;` with C's natural alignment
     constant(name)      value of a #define (an integer or a float) or of an enumerator of an anonymous enum
-    extension_prototypes(), extension_signatures()   the same two tables for the headers mtgs_rast.h includes (EXTENSION_HEADERS)
+    included_headers()  the names on the #include "mtgs_*.h" lines of mtgs_rast.h, in order: one group of entry points each
     header_abi(name)    the whole Abi tuple (prototypes, signatures, structs, constants) of ONE named header that mtgs_rast.h includes
 
 A few regular expressions over a header this project owns, not a C parser: anything they do not recognise raises with the line
@@ -22,9 +22,6 @@ from typing import NamedTuple
 import numpy as np
 
 HEADER = Path(__file__).resolve().parent.parent / "include" / "mtgs_rast.h"
-# additive blocks that are headers of their own (mtgs_rast.h includes them): read by the same parser, bound by _lib.load() like
-# the rest, kept apart from prototypes() / signatures(), which describe mtgs_rast.h's own text
-EXTENSION_HEADERS = ("mtgs_crop.h",)
 
 # by-value scalars: C type -> (ctypes type, numpy format, letter of tests/golden/abi_signatures.txt)
 _SCALARS = {"int": (C.c_int, "<i4", "i"), "int32_t": (C.c_int, "<i4", "i"), "int64_t": (C.c_int64, "<i8", "l"),
@@ -144,36 +141,23 @@ def _header() -> Abi:
 
 
 @lru_cache(maxsize=None)
-def _extensions() -> Abi:
-    abi = Abi({}, {}, {}, {})
-    for name in EXTENSION_HEADERS:
-        part = parse((HEADER.parent / name).read_text())
-        for mine, theirs in zip(abi, part):
-            mine.update(theirs)
-    return abi
+def included_headers() -> tuple:
+    """The additive blocks that are headers of their own, in the order mtgs_rast.h includes them.  Each is read by the same
+    parser (header_abi), bound by _lib.load() and keeps a reviewed record of its own, tests/golden/abi_signatures_<x>.txt."""
+    return tuple(re.findall(r'^#\s*include\s+"(mtgs_\w+\.h)"', HEADER.read_text(), re.M))
 
 
 @lru_cache(maxsize=None)
 def header_abi(name: str) -> Abi:
     """What the included header include/`name` declares by itself: the same Abi tuple as for mtgs_rast.h, structs and constants
-    included.  For additive blocks that keep a reviewed record of their own (include/mtgs_refine_scene.h) and are no part of
-    EXTENSION_HEADERS."""
-    if not any(re.fullmatch(r'#\s*include\s+"%s".*' % re.escape(name), line.strip()) for line in HEADER.read_text().splitlines()):
+    included."""
+    if name not in included_headers():
         raise ValueError(f"{HEADER.name} does not include {name!r}")
     return parse((HEADER.parent / name).read_text())
 
 
 def prototypes() -> dict:
     return _header().prototypes
-
-
-def extension_prototypes() -> dict:
-    """{name: (restype, [argtypes])} of the entry points the EXTENSION_HEADERS declare"""
-    return _extensions().prototypes
-
-
-def extension_signatures() -> dict:
-    return _extensions().signatures
 
 
 def signatures() -> dict:

@@ -25,30 +25,13 @@ def use_library(path) -> None:
         raise RuntimeError("use_library() after the library was loaded")
     LIB_PATH = Path(path)
 
-# include/mtgs_rast.h (and the headers it includes, below) is the description of the ABI: argument and result types of every entry
-# point are read from its prototypes
-_PROTOTYPES = _abi.prototypes()
-EXPORTS = list(_PROTOTYPES)
-_EXTENSION_PROTOTYPES = _abi.extension_prototypes()     # the headers mtgs_rast.h includes (include/mtgs_crop.h)
-EXTENSION_EXPORTS = list(_EXTENSION_PROTOTYPES)
-REFINE_SCENE_HEADER = "mtgs_refine_scene.h"             # a third group, with a record of its own (densify.refine_scene)
-_REFINE_SCENE_PROTOTYPES = _abi.header_abi(REFINE_SCENE_HEADER).prototypes
-REFINE_SCENE_EXPORTS = list(_REFINE_SCENE_PROTOTYPES)
-PRESENT_HEADER = "mtgs_present.h"                       # a fourth group, with a record of its own (mtgs_amd.present)
-_PRESENT_PROTOTYPES = _abi.header_abi(PRESENT_HEADER).prototypes
-PRESENT_EXPORTS = list(_PRESENT_PROTOTYPES)
-LPIPS_HEADER = "mtgs_lpips.h"                           # a fifth group, with a record of its own (mtgs_amd.lpips)
-_LPIPS_PROTOTYPES = _abi.header_abi(LPIPS_HEADER).prototypes
-LPIPS_EXPORTS = list(_LPIPS_PROTOTYPES)
-DINO_HEADER = "mtgs_dino.h"                             # a sixth group, with a record of its own (mtgs_amd.dino)
-_DINO_PROTOTYPES = _abi.header_abi(DINO_HEADER).prototypes
-DINO_EXPORTS = list(_DINO_PROTOTYPES)
-JPEG_HEADER = "mtgs_jpeg.h"                             # a seventh group, with a record of its own (mtgs_amd.jpeg)
-_JPEG_PROTOTYPES = _abi.header_abi(JPEG_HEADER).prototypes
-JPEG_EXPORTS = list(_JPEG_PROTOTYPES)
-LIDAR_HEADER = "mtgs_lidar.h"                           # an eighth group, with a record of its own (mtgs_amd.lidar)
-_LIDAR_PROTOTYPES = _abi.header_abi(LIDAR_HEADER).prototypes
-LIDAR_EXPORTS = list(_LIDAR_PROTOTYPES)
+# include/mtgs_rast.h and the headers it includes are the description of the ABI: argument and result types of every entry point are
+# read from their prototypes.  One group per header, the main header's own declarations first
+_PROTOTYPES = {_abi.HEADER.name: _abi.prototypes()}
+for _name in _abi.included_headers():
+    _PROTOTYPES[_name] = _abi.header_abi(_name).prototypes
+GROUPS = {header: list(group) for header, group in _PROTOTYPES.items()}       # header name -> its entry points
+EXPORTS = GROUPS[_abi.HEADER.name]
 ABI_VERSION = _abi.constant("MTGS_RAST_ABI_VERSION")
 HOT_ABI_VERSION = _abi.constant("MTGS_RAST_HOT_ABI_VERSION")      # hot-path subset: what profiles/rNN_pmc_step.json is keyed on
 
@@ -65,11 +48,11 @@ def load() -> C.CDLL:
             f"{LIB_PATH} is missing: build it with `python -m mtgs_amd.build` (needs hipcc). "
             "mtgs_amd has no CPU or PyTorch fallback for the rasterizer.")
     lib = C.CDLL(str(LIB_PATH))
-    for name, (restype, argtypes) in {**_PROTOTYPES, **_EXTENSION_PROTOTYPES, **_REFINE_SCENE_PROTOTYPES, **_PRESENT_PROTOTYPES,
-                                      **_LPIPS_PROTOTYPES, **_DINO_PROTOTYPES, **_JPEG_PROTOTYPES, **_LIDAR_PROTOTYPES}.items():
-        fn = getattr(lib, name)
-        fn.argtypes = argtypes
-        fn.restype = restype
+    for group in _PROTOTYPES.values():
+        for name, (restype, argtypes) in group.items():
+            fn = getattr(lib, name)
+            fn.argtypes = argtypes
+            fn.restype = restype
     v = lib.mtgs_rast_version()
     if v != ABI_VERSION:
         raise RuntimeError(f"libmtgs_rast.so ABI version {v} != expected {ABI_VERSION}; rebuild")
@@ -135,6 +118,20 @@ def workspace(name: str, *dims, device, dtype, pad: int = 0) -> torch.Tensor:
     *_workspace_floats entry points, torch.uint8 for the *_workspace_bytes ones.  `pad` more elements for a caller that
     aligns the pointer itself."""
     return torch.empty(size_query(name, *dims) + pad, dtype=dtype, device=device)
+
+
+_scratch: dict = {}     # (device, stream) + key -> uint8 tensor
+
+
+def scratch(key: tuple, nbytes, device, stream) -> torch.Tensor:
+    """The cached uint8 scratch tensor of one operator on one stream: allocated on the first call with (device, stream) + key and
+    returned again after that, so that a repeated call allocates nothing and two streams never share a buffer.  `nbytes` is a
+    number or a callable that returns it (a size query, made on a miss only)."""
+    key = (device, stream) + key
+    ws = _scratch.get(key)
+    if ws is None:
+        ws = _scratch[key] = torch.empty(nbytes() if callable(nbytes) else nbytes, dtype=torch.uint8, device=device)
+    return ws
 
 
 def require_gpu(*tensors) -> None:

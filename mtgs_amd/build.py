@@ -96,7 +96,8 @@ def build(force: bool = False, verbose: bool = False) -> Path:
         return r.stderr
 
     if jobs:
-        with ThreadPoolExecutor(max_workers=min(len(jobs), os.cpu_count() or 4)) as ex:
+        # at most 16 compilers at once: a shared machine reports every CPU it has, not the few a process may use
+        with ThreadPoolExecutor(max_workers=min(len(jobs), os.cpu_count() or 4, 16)) as ex:
             for warn in ex.map(run, jobs):
                 if verbose and warn:
                     print(warn, file=sys.stderr)

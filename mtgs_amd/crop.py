@@ -22,22 +22,10 @@ import numpy as np
 import torch
 from torch import Tensor
 
+from ._inputs import point_rows, row_stride
 from ._lib import call, ptr, require_gpu, stream_of, workspace
 
 MAX_TENSORS = 16       # rows of one mtgs_crop_gather table
-
-
-def _points(points: Tensor) -> Tensor:
-    """float32 rows [N, 3] whose three coordinates are adjacent; a row stride >= 3 is kept, so a [N, 4][:, :3] view is read in
-    place.  Any other layout (a column stride, whatever N) is copied."""
-    if points.dim() != 2 or points.shape[1] != 3:
-        raise ValueError(f"points must be [N, 3], got {tuple(points.shape)}")
-    p = points.detach()
-    if p.dtype != torch.float32:
-        p = p.to(torch.float32)
-    if p.stride(1) != 1 or (p.shape[0] > 1 and p.stride(0) < 3):
-        p = p.contiguous()
-    return p
 
 
 def _inside(q: Tensor, h: Tensor) -> Tensor:
@@ -88,8 +76,8 @@ class OrientedBox:
         order, kept iff -h_k < q_k < h_k for every k.  On a GPU tensor this is mtgs_crop_select; on a CPU tensor the same
         operations in the same order in torch, so both give the same decision for every point."""
         if points.is_cuda:
-            return _select(_points(points), self, want_mask=True)[2].to(torch.bool)
-        p = _points(points)
+            return _select(point_rows(points), self, want_mask=True)[2].to(torch.bool)
+        p = point_rows(points)
         m, h = torch.from_numpy(self.world_to_box), torch.from_numpy(self.half)
         x, y, z = p[:, 0:1], p[:, 1:2], p[:, 2:3]
         q = ((m[:, 0] * x + m[:, 1] * y) + m[:, 2] * z) + m[:, 3]
@@ -103,7 +91,7 @@ def _select(p: Tensor, box: OrientedBox, want_mask: bool):
     count = torch.empty(1, dtype=torch.int64, device=dev)
     mask = torch.empty(N, dtype=torch.uint8, device=dev) if want_mask else None
     ws = workspace("mtgs_crop_workspace_bytes", N, device=dev, dtype=torch.uint8)
-    call("mtgs_crop_select", N, ptr(p), p.stride(0) if N > 1 else 3, box.box.ctypes.data_as(C.c_void_p), ptr(keep_ids), ptr(count),
+    call("mtgs_crop_select", N, ptr(p), row_stride(p), box.box.ctypes.data_as(C.c_void_p), ptr(keep_ids), ptr(count),
          ptr(mask), ptr(ws), ws.numel(), stream_of(p))
     return keep_ids, count, mask
 
@@ -155,7 +143,7 @@ def crop_gaussians(gaussians: Dict[str, Optional[Tensor]], box: OrientedBox) -> 
     N = means.shape[0]
     rows = [k for k, v in gaussians.items() if k != "node_table" and isinstance(v, Tensor) and v.dim() >= 1 and v.shape[0] == N]
     require_gpu(*(gaussians[k] for k in rows))
-    keep_ids, count, _ = _select(_points(means), box, want_mask=False)
+    keep_ids, count, _ = _select(point_rows(means), box, want_mask=False)
     n_keep = int(count.item())
     out = {k: v for k, v in gaussians.items() if k != "node_table"}
     out.update(zip(rows, gather_rows([gaussians[k] for k in rows], keep_ids, n_keep)))

@@ -300,16 +300,14 @@ size_t stat_part_bytes(int64_t N) { return align256((size_t)bbox_grid(N) * sizeo
 
 }  // namespace
 
-#define CLOUD_NONNULL(fn, p) MTGS_REQUIRE((p) != nullptr, MTGS_EINVAL, "%s: null pointer: %s", fn, #p)
-#define CLOUD_N(fn, N) MTGS_REQUIRE(N >= 0 && N < ((int64_t)1 << 31), MTGS_EINVAL, "%s: N outside [0, 2^31) (%lld)", fn, (long long)N)
 #define CLOUD_NB(fn, nb) \
     MTGS_REQUIRE(nb >= MIN_NB && nb <= MAX_NB, MTGS_EINVAL, "%s: nb_neighbors outside [%d, %d] (%d)", fn, MIN_NB, MAX_NB, nb)
 
 extern "C" int mtgs_cloud_outlier_workspace_bytes(int64_t N, int nb_neighbors, size_t *bytes) {
     const char *fn = "mtgs_cloud_outlier_workspace_bytes";
-    CLOUD_N(fn, N);
+    MTGS_COUNT31(fn, N);
     CLOUD_NB(fn, nb_neighbors);
-    CLOUD_NONNULL(fn, bytes);
+    MTGS_NONNULL(fn, bytes);
     Ws w;
     if (int rc = layout(N > 0 ? N : 1, nullptr, w)) return rc;
     *bytes = w.total + stat_part_bytes(N);
@@ -319,12 +317,12 @@ extern "C" int mtgs_cloud_outlier_workspace_bytes(int64_t N, int nb_neighbors, s
 extern "C" int mtgs_cloud_outlier(int64_t N, int nb_neighbors, double std_ratio, const float *points, int64_t row_stride, double *avg,
                                   double *stats, uint8_t *keep, int32_t *status, void *ws, size_t ws_bytes, void *stream) {
     const char *fn = "mtgs_cloud_outlier";
-    CLOUD_N(fn, N);
+    MTGS_COUNT31(fn, N);
     CLOUD_NB(fn, nb_neighbors);
     if (N == 0) return MTGS_OK;
     MTGS_REQUIRE(row_stride >= 3, MTGS_EINVAL, "%s: row_stride < 3 (%lld)", fn, (long long)row_stride);
-    CLOUD_NONNULL(fn, points); CLOUD_NONNULL(fn, avg); CLOUD_NONNULL(fn, stats); CLOUD_NONNULL(fn, keep); CLOUD_NONNULL(fn, status);
-    CLOUD_NONNULL(fn, ws);
+    MTGS_NONNULL(fn, points); MTGS_NONNULL(fn, avg); MTGS_NONNULL(fn, stats); MTGS_NONNULL(fn, keep); MTGS_NONNULL(fn, status);
+    MTGS_NONNULL(fn, ws);
     Ws w;
     if (int rc = layout(N, ws, w)) return rc;
     const size_t need = w.total + stat_part_bytes(N);
@@ -356,8 +354,8 @@ extern "C" int mtgs_cloud_outlier(int64_t N, int nb_neighbors, double std_ratio,
 
 extern "C" int mtgs_cloud_voxel_workspace_bytes(int64_t N, size_t *bytes) {
     const char *fn = "mtgs_cloud_voxel_workspace_bytes";
-    CLOUD_N(fn, N);
-    CLOUD_NONNULL(fn, bytes);
+    MTGS_COUNT31(fn, N);
+    MTGS_NONNULL(fn, bytes);
     VoxelWs w;
     if (int rc = voxel_layout(N > 0 ? N : 1, nullptr, w)) return rc;
     *bytes = w.bytes;
@@ -368,12 +366,12 @@ extern "C" int mtgs_cloud_voxel(int64_t N, double voxel_size, const float *point
                                 double *out_xyz, double *out_rgb, int32_t *counts, int64_t *out_keys, int32_t *n_voxels,
                                 int32_t *status, void *ws, size_t ws_bytes, void *stream) {
     const char *fn = "mtgs_cloud_voxel";
-    CLOUD_N(fn, N);
+    MTGS_COUNT31(fn, N);
     MTGS_REQUIRE(voxel_size > 0.0 && isfinite(voxel_size), MTGS_EINVAL, "%s: voxel_size must be positive and finite (%g)", fn, voxel_size);
     if (N == 0) return MTGS_OK;
     MTGS_REQUIRE(row_stride >= 3, MTGS_EINVAL, "%s: row_stride < 3 (%lld)", fn, (long long)row_stride);
-    CLOUD_NONNULL(fn, points); CLOUD_NONNULL(fn, colors); CLOUD_NONNULL(fn, out_xyz); CLOUD_NONNULL(fn, out_rgb); CLOUD_NONNULL(fn, counts);
-    CLOUD_NONNULL(fn, n_voxels); CLOUD_NONNULL(fn, status); CLOUD_NONNULL(fn, ws);
+    MTGS_NONNULL(fn, points); MTGS_NONNULL(fn, colors); MTGS_NONNULL(fn, out_xyz); MTGS_NONNULL(fn, out_rgb); MTGS_NONNULL(fn, counts);
+    MTGS_NONNULL(fn, n_voxels); MTGS_NONNULL(fn, status); MTGS_NONNULL(fn, ws);
     VoxelWs w;
     if (int rc = voxel_layout(N, ws, w)) return rc;
     MTGS_REQUIRE(ws_bytes >= w.bytes, MTGS_EWORKSPACE, "%s: workspace %zu < %zu bytes", fn, ws_bytes, w.bytes);

@@ -19,6 +19,11 @@ void mtgs_set_error(const char *fmt, ...);
         }                             \
     } while (0)
 
+// The two checks every launcher makes on its arguments: a pointer that must be there, and a count in [0, 2^31) under its own name.
+#define MTGS_NONNULL(fn, p) MTGS_REQUIRE((p) != nullptr, MTGS_EINVAL, "%s: null pointer: %s", fn, #p)
+#define MTGS_COUNT31(fn, n) \
+    MTGS_REQUIRE((n) >= 0 && (n) < ((int64_t)1 << 31), MTGS_EINVAL, "%s: %s outside [0, 2^31) (%lld)", fn, #n, (long long)(n))
+
 // Launch errors are surfaced without synchronising the device.
 #define MTGS_CHECK_LAUNCH(name)                                              \
     do {                                                                     \

@@ -92,13 +92,11 @@ __global__ __launch_bounds__(GB) void crop_gather_kernel(GatherTable t, int64_t 
 
 }  // namespace
 
-#define CROP_NONNULL(fn, p) MTGS_REQUIRE((p) != nullptr, MTGS_EINVAL, "%s: null pointer: %s", fn, #p)
-#define CROP_N(fn, N) MTGS_REQUIRE(N >= 0 && N < ((int64_t)1 << 31), MTGS_EINVAL, "%s: %s outside [0, 2^31) (%lld)", fn, #N, (long long)N)
 
 extern "C" int mtgs_crop_workspace_bytes(int64_t N, size_t *bytes) {
     const char *fn = "mtgs_crop_workspace_bytes";
-    CROP_N(fn, N);
-    CROP_NONNULL(fn, bytes);
+    MTGS_COUNT31(fn, N);
+    MTGS_NONNULL(fn, bytes);
     *bytes = mtgs_scan::workspace_bytes(N);
     return MTGS_OK;
 }
@@ -106,13 +104,13 @@ extern "C" int mtgs_crop_workspace_bytes(int64_t N, size_t *bytes) {
 extern "C" int mtgs_crop_select(int64_t N, const float *means, int64_t row_stride, const float *box, int32_t *keep_ids,
                                 int64_t *count, uint8_t *mask, void *ws, size_t ws_bytes, void *stream) {
     const char *fn = "mtgs_crop_select";
-    CROP_N(fn, N);
-    CROP_NONNULL(fn, count);
+    MTGS_COUNT31(fn, N);
+    MTGS_NONNULL(fn, count);
     MTGS_REQUIRE(((uintptr_t)count & 7) == 0, MTGS_EINVAL, "%s: count must be 8-byte aligned", fn);
     hipStream_t st = (hipStream_t)stream;
     if (N == 0) return mtgs_zero_async(count, sizeof(int64_t), st);
     MTGS_REQUIRE(row_stride >= 3, MTGS_EINVAL, "%s: row_stride < 3 (%lld)", fn, (long long)row_stride);
-    CROP_NONNULL(fn, means); CROP_NONNULL(fn, box); CROP_NONNULL(fn, keep_ids); CROP_NONNULL(fn, ws);
+    MTGS_NONNULL(fn, means); MTGS_NONNULL(fn, box); MTGS_NONNULL(fn, keep_ids); MTGS_NONNULL(fn, ws);
     const size_t need = mtgs_scan::workspace_bytes(N);
     MTGS_REQUIRE(ws_bytes >= need, MTGS_EWORKSPACE, "%s: workspace %zu < %zu bytes", fn, ws_bytes, need);
     MTGS_REQUIRE(((uintptr_t)ws & 7) == 0, MTGS_EINVAL, "%s: workspace must be 8-byte aligned", fn);
@@ -127,16 +125,16 @@ extern "C" int mtgs_crop_select(int64_t N, const float *means, int64_t row_strid
 extern "C" int mtgs_crop_gather(int64_t n_keep, int64_t n_rows, const int32_t *keep_ids, int n_tensors, const uint64_t *src,
                                 const uint64_t *dst, const int64_t *row_bytes, void *stream) {
     const char *fn = "mtgs_crop_gather";
-    CROP_N(fn, n_keep);
-    CROP_N(fn, n_rows);
+    MTGS_COUNT31(fn, n_keep);
+    MTGS_COUNT31(fn, n_rows);
     MTGS_REQUIRE(n_tensors >= 1 && n_tensors <= MAX_TENSORS, MTGS_EINVAL, "%s: n_tensors outside [1, %d] (%d)", fn, MAX_TENSORS, n_tensors);
     MTGS_REQUIRE(n_keep <= n_rows, MTGS_EINVAL, "%s: n_keep %lld > n_rows %lld", fn, (long long)n_keep, (long long)n_rows);
-    CROP_NONNULL(fn, src); CROP_NONNULL(fn, dst); CROP_NONNULL(fn, row_bytes);
+    MTGS_NONNULL(fn, src); MTGS_NONNULL(fn, dst); MTGS_NONNULL(fn, row_bytes);
     for (int j = 0; j < n_tensors; ++j)
         MTGS_REQUIRE(row_bytes[j] >= 4 && row_bytes[j] % 4 == 0 && row_bytes[j] <= ((int64_t)1 << 30), MTGS_EINVAL,
                      "%s: row_bytes[%d] must be a multiple of 4 in [4, 2^30] (%lld)", fn, j, (long long)row_bytes[j]);
     if (n_keep == 0) return MTGS_OK;
-    CROP_NONNULL(fn, keep_ids);
+    MTGS_NONNULL(fn, keep_ids);
     GatherTable t{};
     int64_t blocks = 0;
     for (int j = 0; j < n_tensors; ++j) {

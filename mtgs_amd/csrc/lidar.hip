@@ -158,8 +158,6 @@ __global__ __launch_bounds__(TB) void paint_kernel(int32_t N, const T *__restric
 
 }  // namespace
 
-#define LIDAR_NONNULL(fn, p) MTGS_REQUIRE((p) != nullptr, MTGS_EINVAL, "%s: null pointer: %s", fn, #p)
-#define LIDAR_N(fn, N) MTGS_REQUIRE(N >= 0 && N < ((int64_t)1 << 31), MTGS_EINVAL, "%s: N outside [0, 2^31) (%lld)", fn, (long long)N)
 #define LIDAR_HW(fn, h, w)                                                                                                     \
     MTGS_REQUIRE(h >= 1 && w >= 1 && (int64_t)h * w < ((int64_t)1 << 31), MTGS_EINVAL, "%s: h and w must be >= 1 and h * w < 2^31 (%d x %d)", \
                  fn, h, w)
@@ -167,7 +165,7 @@ __global__ __launch_bounds__(TB) void paint_kernel(int32_t N, const T *__restric
 extern "C" int mtgs_lidar_depth_workspace_bytes(int h, int w, size_t *bytes) {
     const char *fn = "mtgs_lidar_depth_workspace_bytes";
     LIDAR_HW(fn, h, w);
-    LIDAR_NONNULL(fn, bytes);
+    MTGS_NONNULL(fn, bytes);
     *bytes = (size_t)h * w * sizeof(int32_t);
     return MTGS_OK;
 }
@@ -176,11 +174,11 @@ extern "C" int mtgs_lidar_depth(int64_t N, const void *points, int points_f64, i
                                 const double *K, int h, int w, float scale, float *depth, int32_t *index, void *ws, size_t ws_bytes,
                                 void *stream) {
     const char *fn = "mtgs_lidar_depth";
-    LIDAR_N(fn, N);
+    MTGS_COUNT31(fn, N);
     LIDAR_HW(fn, h, w);
-    LIDAR_NONNULL(fn, lidar2cam); LIDAR_NONNULL(fn, K); LIDAR_NONNULL(fn, depth); LIDAR_NONNULL(fn, ws);
+    MTGS_NONNULL(fn, lidar2cam); MTGS_NONNULL(fn, K); MTGS_NONNULL(fn, depth); MTGS_NONNULL(fn, ws);
     if (N > 0) {
-        LIDAR_NONNULL(fn, points);
+        MTGS_NONNULL(fn, points);
         MTGS_REQUIRE(row_stride >= 3, MTGS_EINVAL, "%s: row_stride < 3 (%lld)", fn, (long long)row_stride);
     }
     const size_t need = (size_t)h * w * sizeof(int32_t);
@@ -209,13 +207,13 @@ extern "C" int mtgs_lidar_paint(int64_t N, const void *points, int points_f64, i
                                 int h, int w, const uint8_t *images, int reverse_channels, const uint8_t *masks, double *rgb,
                                 int32_t *labels, uint8_t *fov, int32_t *count, void *stream) {
     const char *fn = "mtgs_lidar_paint";
-    LIDAR_N(fn, N);
+    MTGS_COUNT31(fn, N);
     LIDAR_HW(fn, h, w);
     MTGS_REQUIRE(C >= 1 && C <= MTGS_LIDAR_MAX_CAMERAS, MTGS_EINVAL, "%s: C outside [1, %d] (%d)", fn, MTGS_LIDAR_MAX_CAMERAS, C);
     MTGS_REQUIRE((images != nullptr) == (rgb != nullptr), MTGS_EINVAL, "%s: images and rgb go together", fn);
     MTGS_REQUIRE((masks != nullptr) == (labels != nullptr), MTGS_EINVAL, "%s: masks and labels go together", fn);
     if (N == 0) return MTGS_OK;
-    LIDAR_NONNULL(fn, points); LIDAR_NONNULL(fn, lidar2imgs); LIDAR_NONNULL(fn, fov); LIDAR_NONNULL(fn, count);
+    MTGS_NONNULL(fn, points); MTGS_NONNULL(fn, lidar2imgs); MTGS_NONNULL(fn, fov); MTGS_NONNULL(fn, count);
     MTGS_REQUIRE(row_stride >= 3, MTGS_EINVAL, "%s: row_stride < 3 (%lld)", fn, (long long)row_stride);
     hipStream_t st = (hipStream_t)stream;
     const unsigned blocks = (unsigned)ceil_div64(N, TB);

@@ -329,7 +329,6 @@ int check_common(const char *fn, int64_t P, int num_iters, double eps) {
 
 }  // namespace
 
-#define METRICS_NONNULL(fn, p) MTGS_REQUIRE((p) != nullptr, MTGS_EINVAL, "%s: null pointer: %s", fn, #p)
 
 extern "C" int mtgs_metrics_workspace_bytes(int64_t P, int num_iters, size_t *bytes) {
     MTGS_REQUIRE(P >= 0 && num_iters >= 0 && bytes, MTGS_EINVAL,
@@ -343,7 +342,7 @@ extern "C" int mtgs_color_correct(int64_t P, int num_iters, double eps, const fl
     const char *fn = "mtgs_color_correct";
     if (int rc = check_common(fn, P, num_iters, eps)) return rc;
     if (P == 0) return MTGS_OK;
-    METRICS_NONNULL(fn, img); METRICS_NONNULL(fn, ref); METRICS_NONNULL(fn, out); METRICS_NONNULL(fn, ws);
+    MTGS_NONNULL(fn, img); MTGS_NONNULL(fn, ref); MTGS_NONNULL(fn, out); MTGS_NONNULL(fn, ws);
     return run(fn, P, num_iters, eps, img, ref, mask, out, nullptr, nullptr, nullptr, ws, ws_bytes, stream);
 }
 
@@ -354,6 +353,6 @@ extern "C" int mtgs_image_metrics(int64_t P, int num_iters, double eps, const fl
     if (int rc = check_common(fn, P, num_iters, eps)) return rc;
     MTGS_REQUIRE(!pred_depth == !lidar_depth, MTGS_EINVAL, "%s: pred_depth and lidar_depth must be given together", fn);
     if (P == 0) return MTGS_OK;
-    METRICS_NONNULL(fn, pred); METRICS_NONNULL(fn, gt); METRICS_NONNULL(fn, metrics); METRICS_NONNULL(fn, ws);
+    MTGS_NONNULL(fn, pred); MTGS_NONNULL(fn, gt); MTGS_NONNULL(fn, metrics); MTGS_NONNULL(fn, ws);
     return run(fn, P, num_iters, eps, pred, gt, mask, nullptr, pred_depth, lidar_depth, metrics, ws, ws_bytes, stream);
 }

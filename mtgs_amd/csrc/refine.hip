@@ -326,9 +326,6 @@ extern "C" int mtgs_refine_scene_table_bytes(size_t *node_bytes, size_t *move_by
     return MTGS_OK;
 }
 
-#define REFINE_SCENE_PTR(fn, p) \
-    MTGS_REQUIRE(p, MTGS_EINVAL, fn ": null pointer: " #p)
-
 extern "C" int mtgs_refine_scene_classify(int n_nodes, const mtgs_refine_node *table, int64_t total_blocks, int64_t n_total,
                                           int n_columns, int64_t step, int32_t *counts, uint8_t *flags, uint8_t *parents,
                                           void *stream) {
@@ -340,9 +337,9 @@ extern "C" int mtgs_refine_scene_classify(int n_nodes, const mtgs_refine_node *t
     MTGS_REQUIRE(total_blocks >= 0 && total_blocks <= n_total, MTGS_EINVAL,
                  "mtgs_refine_scene_classify: total_blocks outside [0, n_total] (%lld)", (long long)total_blocks);
     if (n_nodes == 0 || n_total == 0 || total_blocks == 0) return MTGS_OK;
-    REFINE_SCENE_PTR("mtgs_refine_scene_classify", table);
-    REFINE_SCENE_PTR("mtgs_refine_scene_classify", counts);
-    REFINE_SCENE_PTR("mtgs_refine_scene_classify", flags);
+    MTGS_NONNULL("mtgs_refine_scene_classify", table);
+    MTGS_NONNULL("mtgs_refine_scene_classify", counts);
+    MTGS_NONNULL("mtgs_refine_scene_classify", flags);
     MTGS_REQUIRE((reinterpret_cast<uintptr_t>(table) & 7) == 0, MTGS_EINVAL, "mtgs_refine_scene_classify: table must be 8-byte aligned");
     refine_scene_classify_kernel<<<(unsigned)total_blocks, 256, 0, (hipStream_t)stream>>>(table, n_nodes, n_total, n_columns,
                                                                                           (uint32_t)step, counts, flags, parents);
@@ -366,13 +363,13 @@ extern "C" int mtgs_refine_scene_apply(int n_nodes, const mtgs_refine_node *tabl
     MTGS_REQUIRE(out_blocks >= 0 && out_blocks <= n_out_total, MTGS_EINVAL,
                  "mtgs_refine_scene_apply: out_blocks outside [0, n_out_total] (%lld)", (long long)out_blocks);
     if (n_nodes == 0 || n_total == 0 || n_out_total == 0 || total_blocks == 0 || out_blocks == 0) return MTGS_OK;
-    REFINE_SCENE_PTR("mtgs_refine_scene_apply", table);
-    REFINE_SCENE_PTR("mtgs_refine_scene_apply", flags);
-    REFINE_SCENE_PTR("mtgs_refine_scene_apply", incl);
-    REFINE_SCENE_PTR("mtgs_refine_scene_apply", src_index);
-    REFINE_SCENE_PTR("mtgs_refine_scene_apply", kind);
-    REFINE_SCENE_PTR("mtgs_refine_scene_apply", out_means);
-    REFINE_SCENE_PTR("mtgs_refine_scene_apply", out_scales);
+    MTGS_NONNULL("mtgs_refine_scene_apply", table);
+    MTGS_NONNULL("mtgs_refine_scene_apply", flags);
+    MTGS_NONNULL("mtgs_refine_scene_apply", incl);
+    MTGS_NONNULL("mtgs_refine_scene_apply", src_index);
+    MTGS_NONNULL("mtgs_refine_scene_apply", kind);
+    MTGS_NONNULL("mtgs_refine_scene_apply", out_means);
+    MTGS_NONNULL("mtgs_refine_scene_apply", out_scales);
     MTGS_REQUIRE((reinterpret_cast<uintptr_t>(table) & 7) == 0, MTGS_EINVAL, "mtgs_refine_scene_apply: table must be 8-byte aligned");
     hipStream_t st = (hipStream_t)stream;
     refine_scene_index_kernel<<<(unsigned)total_blocks, 256, 0, st>>>(table, n_nodes, n_total, flags, incl, src_index, kind);
@@ -388,9 +385,9 @@ extern "C" int mtgs_refine_scene_rows(int n_moves, const mtgs_refine_move *moves
     MTGS_REQUIRE(total_blocks >= 0 && total_blocks < ((int64_t)1 << 31), MTGS_EINVAL,
                  "mtgs_refine_scene_rows: total_blocks outside [0, 2^31) (%lld)", (long long)total_blocks);
     if (n_moves == 0 || total_blocks == 0) return MTGS_OK;
-    REFINE_SCENE_PTR("mtgs_refine_scene_rows", moves);
-    REFINE_SCENE_PTR("mtgs_refine_scene_rows", src_index);
-    REFINE_SCENE_PTR("mtgs_refine_scene_rows", kind);
+    MTGS_NONNULL("mtgs_refine_scene_rows", moves);
+    MTGS_NONNULL("mtgs_refine_scene_rows", src_index);
+    MTGS_NONNULL("mtgs_refine_scene_rows", kind);
     MTGS_REQUIRE((reinterpret_cast<uintptr_t>(moves) & 7) == 0, MTGS_EINVAL, "mtgs_refine_scene_rows: moves must be 8-byte aligned");
     refine_scene_rows_kernel<<<(unsigned)total_blocks, 256, 0, (hipStream_t)stream>>>(moves, n_moves, src_index, kind);
     MTGS_CHECK_LAUNCH("mtgs_refine_scene_rows");

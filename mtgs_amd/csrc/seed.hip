@@ -213,13 +213,12 @@ __global__ __launch_bounds__(TB) void seed_kernel(int64_t N, int k, const float 
 
 }  // namespace
 
-#define SEED_NONNULL(fn, p) MTGS_REQUIRE((p) != nullptr, MTGS_EINVAL, "%s: null pointer: %s", fn, #p)
 
 extern "C" int mtgs_knn_workspace_bytes(int64_t N, int k, size_t *bytes) {
     const char *fn = "mtgs_knn_workspace_bytes";
     MTGS_REQUIRE(N >= 0 && N < ((int64_t)1 << 31), MTGS_EINVAL, "%s: N outside [0, 2^31) (%lld)", fn, (long long)N);
     MTGS_REQUIRE(k >= 1 && k <= MAX_K, MTGS_EINVAL, "%s: k outside [1, %d] (%d)", fn, MAX_K, k);
-    SEED_NONNULL(fn, bytes);
+    MTGS_NONNULL(fn, bytes);
     Ws w;
     if (int rc = layout(N > 0 ? N : 1, nullptr, w)) return rc;
     *bytes = w.total;
@@ -234,7 +233,7 @@ extern "C" int mtgs_knn(int64_t N, int k, const float *points, int64_t row_strid
     if (N == 0) return MTGS_OK;
     MTGS_REQUIRE(N > k, MTGS_EINVAL, "%s: N must exceed k (N = %lld, k = %d)", fn, (long long)N, k);
     MTGS_REQUIRE(row_stride >= 3, MTGS_EINVAL, "%s: row_stride < 3 (%lld)", fn, (long long)row_stride);
-    SEED_NONNULL(fn, points); SEED_NONNULL(fn, dist); SEED_NONNULL(fn, status); SEED_NONNULL(fn, ws);
+    MTGS_NONNULL(fn, points); MTGS_NONNULL(fn, dist); MTGS_NONNULL(fn, status); MTGS_NONNULL(fn, ws);
     Ws w;
     if (int rc = layout(N, ws, w)) return rc;
     MTGS_REQUIRE(ws_bytes >= w.total, MTGS_EWORKSPACE, "%s: workspace %zu < %zu bytes", fn, ws_bytes, w.total);
@@ -266,8 +265,8 @@ extern "C" int mtgs_seed_fwd(int64_t N, int k, const float *knn_dist, const floa
     MTGS_REQUIRE(scale_dim == 1 || scale_dim == 3, MTGS_EINVAL, "%s: scale_dim must be 1 or 3 (%d)", fn, scale_dim);
     MTGS_REQUIRE(dc_row_stride >= 3, MTGS_EINVAL, "%s: dc_row_stride < 3 (%lld)", fn, (long long)dc_row_stride);
     if (N == 0) return MTGS_OK;
-    SEED_NONNULL(fn, knn_dist); SEED_NONNULL(fn, rgb); SEED_NONNULL(fn, scales); SEED_NONNULL(fn, features_dc);
-    SEED_NONNULL(fn, opacities);
+    MTGS_NONNULL(fn, knn_dist); MTGS_NONNULL(fn, rgb); MTGS_NONNULL(fn, scales); MTGS_NONNULL(fn, features_dc);
+    MTGS_NONNULL(fn, opacities);
     MTGS_REQUIRE(!(normals && scale_dim == 3) || quats, MTGS_EINVAL, "%s: null pointer: quats (normals given)", fn);
     seed_kernel<<<(unsigned)ceil_div64(N, TB), TB, 0, (hipStream_t)stream>>>(N, k, knn_dist, rgb, normals, sh_degree, scale_dim, scales,
                                                                            quats, features_dc, dc_row_stride, opacities);

@@ -391,9 +391,8 @@ int check_widths(const char *fn, int n_feat, int n_embed, int n_hidden, int n_ou
 
 }  // namespace
 
-#define WILD_NONNULL(fn, p) MTGS_REQUIRE((p) != nullptr, MTGS_EINVAL, "%s: null pointer: %s", fn, #p)
 #define WILD_WEIGHTS_NONNULL(fn) \
-    WILD_NONNULL(fn, w1); WILD_NONNULL(fn, b1); WILD_NONNULL(fn, w2); WILD_NONNULL(fn, b2); WILD_NONNULL(fn, w3); WILD_NONNULL(fn, b3)
+    MTGS_NONNULL(fn, w1); MTGS_NONNULL(fn, b1); MTGS_NONNULL(fn, w2); MTGS_NONNULL(fn, b2); MTGS_NONNULL(fn, w3); MTGS_NONNULL(fn, b3)
 
 extern "C" int mtgs_wild_workspace_bytes(int64_t cap_rows, size_t *bytes) {
     MTGS_REQUIRE(cap_rows >= 0 && bytes, MTGS_EINVAL, "mtgs_wild_workspace_bytes: cap_rows < 0 or null pointer: bytes");
@@ -412,7 +411,7 @@ extern "C" int mtgs_wild_fwd(int64_t cap_rows, const int32_t *vis_ids, const int
                  "mtgs_wild_fwd: bad sizes (cap_rows >= 0, dc_stride >= 3, rest_stride >= 24, out_stride >= 3)");
     MTGS_REQUIRE(!row_flags || vis_ids, MTGS_EINVAL, "mtgs_wild_fwd: row_flags need vis_ids");
     if (cap_rows == 0) return MTGS_OK;
-    WILD_NONNULL(fn, features_dc); WILD_NONNULL(fn, features_rest); WILD_WEIGHTS_NONNULL(fn); WILD_NONNULL(fn, out);
+    MTGS_NONNULL(fn, features_dc); MTGS_NONNULL(fn, features_rest); WILD_WEIGHTS_NONNULL(fn); MTGS_NONNULL(fn, out);
     MTGS_REQUIRE(!vis_ids || totals, MTGS_EINVAL, "mtgs_wild_fwd: null pointer: totals (vis_ids given)");
     const Weights W{embedding, w1, b1, w2, b2, w3, b3};
     wild_fwd_kernel<<<grid_of(cap_rows), WB, 0, (hipStream_t)stream>>>(Rows{vis_ids, totals, cap_rows}, row_flags, features_dc,
@@ -431,8 +430,8 @@ extern "C" int mtgs_wild_bwd(int64_t cap_rows, const int32_t *vis_ids, const int
     MTGS_REQUIRE(cap_rows >= 0 && grad_stride >= 3 && dc_stride >= 3 && rest_stride >= 24 && d_rest_width >= 24, MTGS_EINVAL,
                  "mtgs_wild_bwd: bad sizes (cap_rows >= 0, grad_stride >= 3, dc_stride >= 3, rest_stride >= 24, d_rest_width >= 24)");
     if (cap_rows == 0) return MTGS_OK;
-    WILD_NONNULL(fn, grad); WILD_NONNULL(fn, features_dc); WILD_NONNULL(fn, features_rest); WILD_WEIGHTS_NONNULL(fn);
-    WILD_NONNULL(fn, d_dc); WILD_NONNULL(fn, d_rest); WILD_NONNULL(fn, partials);
+    MTGS_NONNULL(fn, grad); MTGS_NONNULL(fn, features_dc); MTGS_NONNULL(fn, features_rest); WILD_WEIGHTS_NONNULL(fn);
+    MTGS_NONNULL(fn, d_dc); MTGS_NONNULL(fn, d_rest); MTGS_NONNULL(fn, partials);
     MTGS_REQUIRE(!vis_ids || totals, MTGS_EINVAL, "mtgs_wild_bwd: null pointer: totals (vis_ids given)");
     const int grid = grid_of(cap_rows);
     MTGS_REQUIRE(ws_bytes >= (size_t)grid * PART * sizeof(float), MTGS_EWORKSPACE, "mtgs_wild_bwd: workspace %zu < %zu bytes", ws_bytes,
@@ -451,8 +450,8 @@ extern "C" int mtgs_wild_reduce(int64_t cap_rows, const float *partials, const f
     if (int rc = check_widths(fn, n_feat, n_embed, n_hidden, n_out)) return rc;
     MTGS_REQUIRE(cap_rows >= 0, MTGS_EINVAL, "mtgs_wild_reduce: cap_rows < 0");
     if (cap_rows == 0) return MTGS_OK;
-    WILD_NONNULL(fn, partials); WILD_NONNULL(fn, w1); WILD_NONNULL(fn, d_w1); WILD_NONNULL(fn, d_b1); WILD_NONNULL(fn, d_w2);
-    WILD_NONNULL(fn, d_b2); WILD_NONNULL(fn, d_w3); WILD_NONNULL(fn, d_b3);
+    MTGS_NONNULL(fn, partials); MTGS_NONNULL(fn, w1); MTGS_NONNULL(fn, d_w1); MTGS_NONNULL(fn, d_b1); MTGS_NONNULL(fn, d_w2);
+    MTGS_NONNULL(fn, d_b2); MTGS_NONNULL(fn, d_w3); MTGS_NONNULL(fn, d_b3);
     MTGS_REQUIRE(!d_embed || embedding, MTGS_EINVAL, "mtgs_wild_reduce: null pointer: embedding (d_embed given)");
     wild_reduce_kernel<<<(unsigned)ceil_div64(OFF_B3 + NO, RB) + 1, RB, 0, (hipStream_t)stream>>>(
         grid_of(cap_rows), partials, embedding, w1, d_w1, d_b1, d_w2, d_b2, d_w3, d_b3, d_embed);

@@ -26,8 +26,8 @@ import torch
 from torch import Tensor
 
 from ._abi import header_abi
-from ._lib import call, ptr, require_gpu, size_query, stream_of
-from .loss import _as_f32, _mask_u8
+from ._inputs import as_f32, image_pair, mask_u8
+from ._lib import call, ptr, require_gpu, scratch, size_query, stream_of
 
 _ABI = header_abi("mtgs_dino.h")
 _CONFIG = _ABI.structs["mtgs_dino_config"]
@@ -281,7 +281,6 @@ def resample_tables(H: int, W: int, S: int):
 
 
 _tables: dict = {}          # (H, W, S, device) -> (int32 device tensor, hk, vk)
-_workspaces: dict = {}      # (config, device) -> uint8 tensor
 
 
 def _device_tables(H: int, W: int, S: int, device):
@@ -297,32 +296,21 @@ def _device_tables(H: int, W: int, S: int, device):
     return t
 
 
-def _workspace(cfg: DinoConfig, device) -> Tensor:
-    key = (cfg, device)
-    ws = _workspaces.get(key)
-    if ws is None:
-        c = cfg.struct()                            # alive until the call returns
-        ws = _workspaces[key] = torch.empty(size_query("mtgs_dino_workspace_bytes", _cfg_ptr(c)), dtype=torch.uint8, device=device)
-    return ws
+def workspace_bytes(cfg: DinoConfig) -> int:
+    c = cfg.struct()                                # alive until the call returns
+    return size_query("mtgs_dino_workspace_bytes", _cfg_ptr(c))
+
+
+def _scratch(cfg: DinoConfig, device, stream) -> Tensor:
+    return scratch(("dino", cfg), lambda: workspace_bytes(cfg), device, stream)
 
 
 # ---- the operators -----------------------------------------------------------------------------------------------------------------
 def _images(pred: Tensor, gt: Tensor, mask: Optional[Tensor]):
-    if pred.dim() != 3:
-        raise ValueError(f"pred must be [H, W, C], got {tuple(pred.shape)}")
-    if pred.shape[-1] != 3:
-        raise NotImplementedError(f"pred has {pred.shape[-1]} channels: only 3-channel images are implemented")
-    if pred.shape != gt.shape:
-        raise ValueError(f"pred {tuple(pred.shape)} and gt {tuple(gt.shape)} must have the same shape")
-    if torch.is_grad_enabled() and (pred.requires_grad or gt.requires_grad):
-        raise RuntimeError("dinov2_sim is a metric here, forward only: an input requires grad (detach it or call under torch.no_grad())")
-    H, W = pred.shape[:2]
-    if H < 1 or W < 1:
+    pred_c, gt_c, mask_c = image_pair(pred, gt, mask, metric="dinov2_sim")
+    if pred_c.numel() == 0:
         raise ValueError(f"pred must have at least one pixel, got {tuple(pred.shape)}")
-    if mask is not None and mask.numel() != H * W:
-        raise ValueError(f"mask must have H * W = {H * W} elements, got {tuple(mask.shape)}")
-    require_gpu(pred, gt, mask)
-    return _as_f32(pred), _as_f32(gt), _mask_u8(mask, H, W)
+    return pred_c, gt_c, mask_c
 
 
 def _check_weights(weights: "DinoWeights", device) -> None:
@@ -361,7 +349,7 @@ def dino_patch_weights(mask: Optional[Tensor], H: int, W: int, size: int = 518, 
     tables, hk, vk = _device_tables(H, W, size, device)
     G = size // PATCH
     out = torch.empty(G * G + 1, dtype=torch.float32, device=device)
-    call("mtgs_dino_patch_weights", H, W, size, ptr(_mask_u8(mask, H, W)), ptr(tables), hk, vk, ptr(out), torch.cuda.current_stream(device).cuda_stream)
+    call("mtgs_dino_patch_weights", H, W, size, ptr(mask_u8(mask, H, W)), ptr(tables), hk, vk, ptr(out), torch.cuda.current_stream(device).cuda_stream)
     return out
 
 
@@ -382,18 +370,18 @@ def dino_linear(a: Tensor, w: Tensor, bias: Tensor, epilogue: str = "bias", *, g
     if bias.numel() != N:
         raise ValueError(f"bias has {bias.numel()} elements for N = {N}")
     require_gpu(a, w, bias, gamma, residual, pos, cls)
-    a = _as_f32(a)                                  # no copy of an fp32 contiguous array, whatever its alignment
-    w_c, bias_c = _as_f32(w), _as_f32(bias)
+    a = as_f32(a)                                  # no copy of an fp32 contiguous array, whatever its alignment
+    w_c, bias_c = as_f32(w), as_f32(bias)
     tokens, gamma_c, pos_c, cls_c = 0, None, None, None
     if epilogue == "scale_residual":
         if gamma is None or residual is None or gamma.numel() != N or tuple(residual.shape) != (M, N):
             raise ValueError("scale_residual takes gamma [N] and residual [M, N]")
-        gamma_c = _as_f32(gamma)
+        gamma_c = as_f32(gamma)
         out = residual.to(torch.float32).clone(memory_format=torch.contiguous_format)
     elif epilogue == "patch_embed":
         if pos is None or cls is None or pos.dim() != 2 or pos.shape[1] != N or cls.numel() != N or M != 2 * (pos.shape[0] - 1):
             raise ValueError("patch_embed takes pos [T, N], cls [N] and M = 2 (T - 1) rows")
-        tokens, pos_c, cls_c = pos.shape[0], _as_f32(pos), _as_f32(cls)
+        tokens, pos_c, cls_c = pos.shape[0], as_f32(pos), as_f32(cls)
         out = torch.empty(2 * tokens, N, dtype=torch.float32, device=a.device)
     else:
         out = torch.empty(M, N, dtype=torch.float32, device=a.device)
@@ -412,9 +400,9 @@ def dino_layernorm(x: Tensor, weight: Tensor, bias: Tensor, eps: float = 1e-6) -
     if weight.numel() != D or bias.numel() != D:
         raise ValueError(f"weight and bias must have D = {D} elements")
     require_gpu(x, weight, bias)
-    x_c = _as_f32(x)
+    x_c = as_f32(x)
     out = torch.empty_like(x_c)
-    call("mtgs_dino_layernorm", M, D, float(eps), ptr(x_c), ptr(_as_f32(weight)), ptr(_as_f32(bias)), ptr(out), stream_of(x_c))
+    call("mtgs_dino_layernorm", M, D, float(eps), ptr(x_c), ptr(as_f32(weight)), ptr(as_f32(bias)), ptr(out), stream_of(x_c))
     return out
 
 
@@ -423,7 +411,7 @@ def dino_attention(qkv: Tensor, heads: int) -> Tensor:
     if qkv.dim() != 3 or qkv.shape[2] != 3 * heads * HEAD_DIM:
         raise ValueError(f"qkv must be [n, T, 3 * {heads} * {HEAD_DIM}], got {tuple(qkv.shape)}")
     require_gpu(qkv)
-    q = _as_f32(qkv)
+    q = as_f32(qkv)
     n, T, _ = q.shape
     out = torch.empty(n, T, heads * HEAD_DIM, dtype=torch.float32, device=q.device)
     call("mtgs_dino_attention", n, T, heads, ptr(q), ptr(out), stream_of(q))
@@ -437,7 +425,7 @@ def dino_tail(features: Tensor, patch_weights: Tensor) -> Tensor:
     if features.shape[2] > MAX_DIM:
         raise NotImplementedError(f"D = {features.shape[2]} exceeds {MAX_DIM}")
     require_gpu(features, patch_weights)
-    f, w = _as_f32(features), _as_f32(patch_weights)
+    f, w = as_f32(features), as_f32(patch_weights)
     G2, D = f.shape[1], f.shape[2]
     scratch = torch.empty(G2, dtype=torch.float32, device=f.device)
     out = torch.empty((), dtype=torch.float32, device=f.device)
@@ -452,11 +440,12 @@ def dino_features(pred: Tensor, gt: Tensor, *, weights: DinoWeights) -> Tensor:
     cfg = weights.config
     H, W = pred_c.shape[:2]
     tables, hk, vk = _device_tables(H, W, cfg.image, pred_c.device)
-    ws = _workspace(cfg, pred_c.device)
+    stream = stream_of(pred_c)
+    ws = _scratch(cfg, pred_c.device, stream)
     out = torch.empty(2, cfg.patches, cfg.dim, dtype=torch.float32, device=pred_c.device)
     c = cfg.struct()                                # alive until the call returns
     call("mtgs_dino_features", _cfg_ptr(c), H, W, ptr(pred_c), ptr(gt_c), ptr(tables), hk, vk, ptr(weights.flat), ptr(out), ptr(ws),
-         ws.numel(), stream_of(pred_c))
+         ws.numel(), stream)
     return out
 
 
@@ -464,17 +453,18 @@ def dino_similarity(pred: Tensor, gt: Tensor, mask: Optional[Tensor] = None, *, 
     """DINOv2Similarity.similarity(pred, gt, mask) of [H, W, 3] images in [0, 1] (clamped to it) and a mask [H, W, 1] or [H, W]
     bool or uint8 (non-zero = visible; None = all visible): the patch-weighted mean cosine similarity of the two images' patch
     features, exactly 0 when no pixel is visible.  Returns a 0-dim fp32 tensor on the images' device.  The tables are kept per
-    (H, W, image size, device), the workspace per (configuration, device)."""
+    (H, W, image size, device), the workspace per (device, stream, configuration)."""
     pred_c, gt_c, mask_c = _images(pred, gt, mask)
     _check_weights(weights, pred_c.device)
     cfg = weights.config
     H, W = pred_c.shape[:2]
     tables, hk, vk = _device_tables(H, W, cfg.image, pred_c.device)
-    ws = _workspace(cfg, pred_c.device)
+    stream = stream_of(pred_c)
+    ws = _scratch(cfg, pred_c.device, stream)
     out = torch.empty((), dtype=torch.float32, device=pred_c.device)
     c = cfg.struct()                                # alive until the call returns
     call("mtgs_dino_similarity", _cfg_ptr(c), H, W, ptr(pred_c), ptr(gt_c), ptr(mask_c), ptr(tables), hk, vk, ptr(weights.flat),
-         ptr(out), ptr(ws), ws.numel(), stream_of(pred_c))
+         ptr(out), ptr(ws), ws.numel(), stream)
     return out
 
 

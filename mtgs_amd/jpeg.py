@@ -26,13 +26,14 @@ import torch
 from torch import Tensor
 
 from . import _abi
-from ._lib import JPEG_HEADER, PRESENT_HEADER, call, ptr, require_gpu, stream_of
+from ._inputs import shape_of
+from ._lib import call, ptr, require_gpu, scratch, stream_of
 
-_ABI = _abi.header_abi(JPEG_HEADER)
+_ABI = _abi.header_abi("mtgs_jpeg.h")
 HEADER_BYTES = _ABI.constants["MTGS_JPEG_HEADER_BYTES"]
 BLOCK_BITS = _ABI.constants["MTGS_JPEG_BLOCK_BITS"]
 _SUBSAMPLINGS = {"4:2:0": _ABI.constants["MTGS_JPEG_420"], "4:4:4": _ABI.constants["MTGS_JPEG_444"]}
-_CONVERSIONS = {k: _abi.header_abi(PRESENT_HEADER).constants["MTGS_PRESENT_U8_" + k.upper()] for k in ("truncate", "round")}
+_CONVERSIONS = {k: _abi.header_abi("mtgs_present.h").constants["MTGS_PRESENT_U8_" + k.upper()] for k in ("truncate", "round")}
 
 
 @dataclass
@@ -90,9 +91,8 @@ def header(h: int, w: int, quality: int = 75, subsampling: str = "4:2:0") -> byt
     return bytes(buf)
 
 
-# ---- uploaded once per (h, w, quality, subsampling, device); allocated once per (device, stream, h, w, subsampling) ----------------
+# ---- uploaded once per (h, w, quality, subsampling, device) ------------------------------------------------------------------------
 _DEVICE_HEADERS: Dict[tuple, Tensor] = {}
-_WORKSPACES: Dict[tuple, Tensor] = {}
 
 
 def _device_header(h, w, quality, subsampling, device) -> Tensor:
@@ -100,13 +100,6 @@ def _device_header(h, w, quality, subsampling, device) -> Tensor:
     if key not in _DEVICE_HEADERS:
         _DEVICE_HEADERS[key] = torch.from_numpy(np.frombuffer(header(h, w, quality, subsampling), dtype=np.uint8).copy()).to(device)
     return _DEVICE_HEADERS[key]
-
-
-def _workspace(h, w, subsampling, device, stream) -> Tensor:
-    key = (device, stream, h, w, subsampling)
-    if key not in _WORKSPACES:
-        _WORKSPACES[key] = torch.empty(sizes(h, w, subsampling)[0], dtype=torch.uint8, device=device)
-    return _WORKSPACES[key]
 
 
 def encode_jpeg(image: Tensor, quality: int = 75, subsampling: str = "4:2:0", *, conversion: str = "truncate",
@@ -118,7 +111,7 @@ def encode_jpeg(image: Tensor, quality: int = 75, subsampling: str = "4:2:0", *,
     in place.  Anything else JPEG offers (other channel counts, 4:2:2, optimize, progressive) raises NotImplementedError."""
     _check_options(quality, subsampling, conversion, options)
     if not isinstance(image, Tensor) or image.dim() != 3:
-        raise ValueError(f"image must be a [H, W, 3] tensor, got {tuple(image.shape) if isinstance(image, Tensor) else type(image).__name__}")
+        raise ValueError(f"image must be a [H, W, 3] tensor, got {shape_of(image)}")
     if image.shape[2] != 3:
         raise NotImplementedError(f"encode_jpeg: {image.shape[2]} channel(s) are not implemented (RGB [H, W, 3] only)")
     if image.dtype not in (torch.uint8, torch.float32):
@@ -139,7 +132,7 @@ def encode_jpeg(image: Tensor, quality: int = 75, subsampling: str = "4:2:0", *,
             raise ValueError(f"out must hold a contiguous uint8 [capacity] data and an int64 [2] meta on {device}")
     stream = stream_of(image)
     head = _device_header(h, w, quality, subsampling, device)
-    ws = _workspace(h, w, subsampling, device, stream)
+    ws = scratch(("jpeg", h, w, subsampling), lambda: sizes(h, w, subsampling)[0], device, stream)      # once per stream and shape
     if out is None:
         capacity = sizes(h, w, subsampling)[1] if capacity is None else int(capacity)
         if capacity < 0:

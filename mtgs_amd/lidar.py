@@ -22,9 +22,10 @@ import torch
 from torch import Tensor
 
 from . import _abi
-from ._lib import LIDAR_HEADER, call, ptr, require_gpu, stream_of, workspace
+from ._inputs import point_rows, row_stride, shape_of
+from ._lib import call, ptr, require_gpu, stream_of, workspace
 
-MAX_CAMERAS = _abi.header_abi(LIDAR_HEADER).constants["MTGS_LIDAR_MAX_CAMERAS"]
+MAX_CAMERAS = _abi.header_abi("mtgs_lidar.h").constants["MTGS_LIDAR_MAX_CAMERAS"]
 _FLOATS = (torch.float32, torch.float64)
 
 
@@ -37,25 +38,18 @@ class PaintedPoints(NamedTuple):
     count: Tensor
 
 
-def _points(points: Tensor) -> Tensor:
-    """float32 or float64 rows whose three coordinates are contiguous; the row stride is kept (a [N, 4][:, :3] view is read in
-    place), as seed._points does for float32"""
-    if not isinstance(points, Tensor) or points.dim() != 2 or points.shape[1] != 3:
-        raise ValueError(f"points must be [N, 3], got {tuple(points.shape) if isinstance(points, Tensor) else type(points).__name__}")
-    if points.dtype not in _FLOATS:
-        raise TypeError(f"points must be float32 or float64, got {points.dtype}")
-    if points.shape[0] >= 1 << 31:
+def _sweep(points: Tensor) -> Tensor:
+    """the rows of a sweep in their own precision (_inputs.point_rows), fewer than 2^31 of them"""
+    p = point_rows(points, _FLOATS, convert=False)
+    if p.shape[0] >= 1 << 31:
         raise ValueError(f"points must have fewer than 2^31 rows, got {tuple(points.shape)}")
-    p = points.detach()
-    if p.shape[0] > 1 and (p.stride(1) != 1 or p.stride(0) < 3):
-        p = p.contiguous()
     return p
 
 
 def _check_matrix(m, name: str, batched: bool) -> None:
     want = "[C, 4, 4] or [C, 3, 4]" if batched else "[4, 4] or [3, 4]"
     if not isinstance(m, Tensor) or m.dim() != 2 + batched or tuple(m.shape[-2:]) not in ((4, 4), (3, 4)):
-        raise ValueError(f"{name} must be {want}, got {tuple(m.shape) if isinstance(m, Tensor) else type(m).__name__}")
+        raise ValueError(f"{name} must be {want}, got {shape_of(m)}")
     if m.dtype not in _FLOATS:
         raise TypeError(f"{name} must be float32 or float64, got {m.dtype}")
 
@@ -79,10 +73,10 @@ def depth_image(points: Tensor, lidar2cam: Tensor, K: Tensor, width: int, height
     lies in [0, W) x [0, H) writes its depth at ((int)u, (int)v); among the points of one pixel the LARGEST index wins (NumPy's
     assignment); the image is multiplied by `scale` in float32; pixels without a point are 0.  A non-finite point writes nothing.
     With return_index also the winning point's index, int32 [H, W], -1 where no point landed.  N = 0 gives zeros."""
-    p = _points(points)
+    p = _sweep(points)
     _check_matrix(lidar2cam, "lidar2cam", False)
     if not isinstance(K, Tensor) or tuple(K.shape) != (3, 3):
-        raise ValueError(f"K must be [3, 3], got {tuple(K.shape) if isinstance(K, Tensor) else type(K).__name__}")
+        raise ValueError(f"K must be [3, 3], got {shape_of(K)}")
     if K.dtype not in _FLOATS:
         raise TypeError(f"K must be float32 or float64, got {K.dtype}")
     _size(width, height)
@@ -92,7 +86,7 @@ def depth_image(points: Tensor, lidar2cam: Tensor, K: Tensor, width: int, height
     depth = torch.empty((height, width, 1), dtype=torch.float32, device=dev)
     index = torch.empty((height, width), dtype=torch.int32, device=dev) if return_index else None
     ws = workspace("mtgs_lidar_depth_workspace_bytes", height, width, device=dev, dtype=torch.uint8)
-    call("mtgs_lidar_depth", N, ptr(p) if N else None, int(p.dtype == torch.float64), p.stride(0) if N > 1 else 3, ptr(m), ptr(k),
+    call("mtgs_lidar_depth", N, ptr(p) if N else None, int(p.dtype == torch.float64), row_stride(p), ptr(m), ptr(k),
          height, width, float(scale), ptr(depth), ptr(index), ptr(ws), ws.numel(), stream_of(p))
     return (depth, index) if return_index else depth
 
@@ -105,7 +99,7 @@ def paint_points(points: Tensor, lidar2imgs: Tensor, images: Optional[Tensor] = 
     (cv2.imread's, the reference's) reverses the channels, "rgb" keeps them.  sem_masks uint8 [C, H, W, 1] or [C, H, W] are read at
     the nearest texel (ties to even) of the FIRST camera that sees the point: labels int32 [N], 0 where none does.  fov = count >
     0.  One of the two inputs may be missing; the projection is done once for both."""
-    p = _points(points)
+    p = _sweep(points)
     _check_matrix(lidar2imgs, "lidar2imgs", True)
     C = lidar2imgs.shape[0]
     if not 1 <= C <= MAX_CAMERAS:
@@ -115,15 +109,14 @@ def paint_points(points: Tensor, lidar2imgs: Tensor, images: Optional[Tensor] = 
     size = None
     if images is not None:
         if not isinstance(images, Tensor) or images.dim() != 4 or images.shape[0] != C or images.shape[3] != 3:
-            raise ValueError(f"images must be [C, H, W, 3] with C = {C}, got {tuple(images.shape) if isinstance(images, Tensor) else type(images).__name__}")
+            raise ValueError(f"images must be [C, H, W, 3] with C = {C}, got {shape_of(images)}")
         if images.dtype != torch.uint8:
             raise TypeError(f"images must be uint8, got {images.dtype}")
         size = tuple(images.shape[1:3])
     if sem_masks is not None:
         ok = isinstance(sem_masks, Tensor) and sem_masks.shape[0:1] == (C,) and (sem_masks.dim() == 3 or (sem_masks.dim() == 4 and sem_masks.shape[3] == 1))
         if not ok:
-            raise ValueError(f"sem_masks must be [C, H, W, 1] or [C, H, W] with C = {C}, got "
-                             f"{tuple(sem_masks.shape) if isinstance(sem_masks, Tensor) else type(sem_masks).__name__}")
+            raise ValueError(f"sem_masks must be [C, H, W, 1] or [C, H, W] with C = {C}, got {shape_of(sem_masks)}")
         if sem_masks.dtype != torch.uint8:
             raise TypeError(f"sem_masks must be uint8, got {sem_masks.dtype}")
         if size is not None and tuple(sem_masks.shape[1:3]) != size:
@@ -143,6 +136,6 @@ def paint_points(points: Tensor, lidar2imgs: Tensor, images: Optional[Tensor] = 
     fov = torch.empty(N, dtype=torch.bool, device=dev)
     count = torch.empty(N, dtype=torch.int32, device=dev)
     if N > 0:
-        call("mtgs_lidar_paint", N, ptr(p), int(p.dtype == torch.float64), p.stride(0) if N > 1 else 3, C, ptr(m), h, w, ptr(img),
+        call("mtgs_lidar_paint", N, ptr(p), int(p.dtype == torch.float64), row_stride(p), C, ptr(m), h, w, ptr(img),
              int(channel_order == "bgr"), ptr(msk), ptr(rgb), ptr(labels), ptr(fov), ptr(count), stream_of(p))
     return PaintedPoints(rgb, labels, fov, count)

@@ -16,22 +16,8 @@ import torch
 from torch import Tensor
 
 from ._abi import constant, struct_dtype
+from ._inputs import as_f32, mask_u8
 from ._lib import call, ptr, require_gpu, stream_of, workspace
-
-
-def _mask_u8(mask: Optional[Tensor], H: int, W: int) -> Optional[Tensor]:
-    """[H,W] uint8 view of a pixel mask for the kernels.  A bool mask is REINTERPRETED (True is the byte 1): `.to(torch.uint8)`
-    is a copy kernel, and the loss head takes the same mask four or five times per iteration."""
-    if mask is None:
-        return None
-    m = mask.reshape(H, W).contiguous()
-    return m.view(torch.uint8) if m.dtype == torch.bool else m.to(torch.uint8)
-
-
-def _as_f32(t: Tensor, *shape) -> Tensor:
-    """The detached fp32 contiguous array (reshaped to `shape` when given) a kernel reads: no copy when `t` already is one."""
-    t = t.detach().to(torch.float32)
-    return (t.reshape(shape) if shape else t).contiguous()
 
 
 def _cotangent(v_out: Tensor) -> Tensor:
@@ -44,9 +30,9 @@ class _MaskedSSIM(torch.autograd.Function):
     def forward(ctx, gt, pred, mask, win_sigma, data_range, K1, K2):
         require_gpu(gt, pred, mask)
         H, W = pred.shape[:2]
-        gt_c = _as_f32(gt)
-        pred_c = _as_f32(pred)
-        mask_c = _mask_u8(mask, H, W)
+        gt_c = as_f32(gt)
+        pred_c = as_f32(pred)
+        mask_c = mask_u8(mask, H, W)
         dev = pred.device
         partials = workspace("mtgs_ssim_workspace_floats", W, H, device=dev, dtype=torch.float32)
         out = torch.empty(2, dtype=torch.float32, device=dev)
@@ -92,9 +78,9 @@ class _MaskedL1(torch.autograd.Function):
     def forward(ctx, gt, pred, mask):
         require_gpu(gt, pred, mask)
         H, W = pred.shape[:2]
-        gt_c = _as_f32(gt)
-        pred_c = _as_f32(pred)
-        mask_c = _mask_u8(mask, H, W)
+        gt_c = as_f32(gt)
+        pred_c = as_f32(pred)
+        mask_c = mask_u8(mask, H, W)
         partials = workspace("mtgs_l1_workspace_floats", W, H, device=pred.device, dtype=torch.float32)
         out = torch.empty(2, dtype=torch.float32, device=pred.device)
         ch = pred.shape[2]
@@ -132,9 +118,9 @@ class _InverseDepthL1(torch.autograd.Function):
     def forward(ctx, gt_depth, depth, mask, lo, hi, eps):
         require_gpu(gt_depth, depth, mask)
         H, W = depth.shape[:2]
-        gt_c = _as_f32(gt_depth, H, W)
-        d_c = _as_f32(depth, H, W)
-        mask_c = _mask_u8(mask, H, W)
+        gt_c = as_f32(gt_depth, H, W)
+        d_c = as_f32(depth, H, W)
+        mask_c = mask_u8(mask, H, W)
         partials = workspace("mtgs_l1_workspace_floats", W, H, device=depth.device, dtype=torch.float32)
         out = torch.empty(2, dtype=torch.float32, device=depth.device)
         used = torch.empty((H, W), dtype=torch.uint8, device=depth.device)
@@ -184,10 +170,10 @@ class _PseudoDepthLoss(torch.autograd.Function):
     def forward(ctx, pred, gt, mask, rgb, kind, lo, hi, thresh):
         require_gpu(pred, gt, mask, rgb)
         H, W = pred.shape[:2]
-        p_c = _as_f32(pred, H, W)
-        g_c = _as_f32(gt, H, W)
-        m_c = _mask_u8(mask, H, W)
-        rgb_c = None if rgb is None else _as_f32(rgb, H, W, 3)
+        p_c = as_f32(pred, H, W)
+        g_c = as_f32(gt, H, W)
+        m_c = mask_u8(mask, H, W)
+        rgb_c = None if rgb is None else as_f32(rgb, H, W, 3)
         partials = workspace("mtgs_depth_loss_workspace_floats", W, H, device=pred.device, dtype=torch.float32)
         out = torch.empty(_DEPTH_LOSS_RECORD, dtype=torch.float32, device=pred.device)
         call("mtgs_depth_loss_fwd", kind, W, H, ptr(p_c), ptr(g_c), ptr(m_c), ptr(rgb_c), lo, hi, thresh, ptr(partials), ptr(out),
@@ -307,10 +293,10 @@ class _OutputHead(torch.autograd.Function):
         D = render.shape[-1]
         H, W = render.shape[-3], render.shape[-2]
         dev = render.device
-        r_c = _as_f32(render, H, W, D)
-        a_c = _as_f32(alpha, H, W)
-        bg_c = _as_f32(background, 3)
-        e_c = None if exposure is None else _as_f32(exposure, 12)
+        r_c = as_f32(render, H, W, D)
+        a_c = as_f32(alpha, H, W)
+        bg_c = as_f32(background, 3)
+        e_c = None if exposure is None else as_f32(exposure, 12)
         depth_ch = D - 1 if want_depth else -1
         dmax = r_c[..., depth_ch].max().reshape(1) if want_depth else None      # depth_im.detach().max() (:680)
         rgb = torch.empty((H, W, 3), dtype=torch.float32, device=dev)
@@ -378,8 +364,8 @@ class _OobLoss(torch.autograd.Function):
         if load().mtgs_oob_desc_bytes() != _OOB_DESC.itemsize:
             raise RuntimeError("mtgs_oob_desc layout mismatch between libmtgs_rast.so and mtgs_amd.loss")
         n_nodes, dev = len(flat) // 2, radii.device
-        means = [_as_f32(m) for m in flat[0::2]]
-        opacs = [_as_f32(o, -1) for o in flat[1::2]]
+        means = [as_f32(m) for m in flat[0::2]]
+        opacs = [as_f32(o, -1) for o in flat[1::2]]
         n = np.asarray([m.shape[0] for m in means], dtype=np.int64)
         r = radii.reshape(-1)
         r = (r if r.dtype == torch.int32 else r.to(torch.int32)).contiguous()
@@ -445,9 +431,9 @@ class _DepthNcc(torch.autograd.Function):
         require_gpu(pred, gt, mask)
         H, W = pred.shape[0], pred.shape[1]
         dev = pred.device
-        p_c = _as_f32(pred, H, W)
-        g_c = _as_f32(gt, H, W)
-        m_c = _mask_u8(mask, H, W)
+        p_c = as_f32(pred, H, W)
+        g_c = as_f32(gt, H, W)
+        m_c = mask_u8(mask, H, W)
         n = C.c_int64(0)
         call("mtgs_ncc_patches", W, H, patch_size, stride, C.byref(n))
         stats = torch.empty(n.value * 6, dtype=torch.float32, device=dev)
@@ -488,7 +474,7 @@ class _TvLoss(torch.autograd.Function):
     def forward(ctx, image):
         require_gpu(image)
         H, W, Cc = image.shape[-3], image.shape[-2], image.shape[-1]
-        x = _as_f32(image, H, W, Cc)
+        x = as_f32(image, H, W, Cc)
         partials = workspace("mtgs_tv_workspace_floats", W, H, Cc, device=x.device, dtype=torch.float32)
         out = torch.empty(1, dtype=torch.float32, device=x.device)
         call("mtgs_tv_fwd", W, H, Cc, ptr(x), ptr(partials), ptr(out), stream_of(x))
@@ -520,12 +506,12 @@ def _intrinsics(K: Tensor) -> Tensor:
     """K [3,3] (or [1,3,3]) as the fp32 row-major device array the kernels read fx, fy, cx, cy from (no host read: a
     float32 contiguous K is passed as it is, so a captured graph sees later writes into it)."""
     assert K.numel() == 9, K.shape
-    return _as_f32(K, 3, 3)
+    return as_f32(K, 3, 3)
 
 
 def _depth_image(depth: Tensor) -> Tensor:
     assert depth.dim() in (2, 3) and depth.numel() == depth.shape[0] * depth.shape[1], depth.shape
-    return _as_f32(depth, depth.shape[0], depth.shape[1])
+    return as_f32(depth, depth.shape[0], depth.shape[1])
 
 
 def normals_from_depth(depth: Tensor, K: Tensor) -> Tensor:
@@ -549,10 +535,10 @@ class _DepthNormalLoss(torch.autograd.Function):
     def forward(ctx, pred, gt_depth, K, mask, lo, hi, tv):
         require_gpu(pred, gt_depth, K, mask)
         H, W = pred.shape[0], pred.shape[1]
-        p_c = _as_f32(pred)
+        p_c = as_f32(pred)
         d_c = _depth_image(gt_depth)
         k_c = _intrinsics(K)
-        m_c = _mask_u8(mask, H, W)
+        m_c = mask_u8(mask, H, W)
         partials = workspace("mtgs_depth_normal_loss_workspace_floats", W, H, device=pred.device, dtype=torch.float32)
         out = torch.empty(4, dtype=torch.float32, device=pred.device)
         call("mtgs_depth_normal_loss_fwd", W, H, ptr(p_c), ptr(d_c), ptr(k_c), ptr(m_c), float(lo), float(hi), int(tv),
@@ -598,7 +584,7 @@ class _ScaleRegularizers(torch.autograd.Function):
     @staticmethod
     def forward(ctx, scales, two_d, max_ratio):
         require_gpu(scales)
-        s = _as_f32(scales)
+        s = as_f32(scales)
         N = s.shape[0]
         partials = workspace("mtgs_scale_reg_workspace_floats", N, device=s.device, dtype=torch.float32)
         out = torch.empty(2, dtype=torch.float32, device=s.device)

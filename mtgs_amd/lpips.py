@@ -23,8 +23,8 @@ from typing import List, Optional, Sequence, Tuple
 import torch
 from torch import Tensor
 
-from ._lib import call, ptr, require_gpu, size_query, stream_of
-from .loss import _as_f32, _mask_u8
+from ._inputs import as_f32, image_pair
+from ._lib import call, ptr, require_gpu, scratch, size_query, stream_of
 
 # (cin, cout, kernel, stride, pad, a 3x3 stride-2 max-pool before it): AlexNet's features, every convolution followed by a ReLU and a tap
 LAYERS = ((3, 64, 11, 4, 2, False), (64, 192, 5, 1, 2, True), (192, 384, 3, 1, 1, True), (384, 256, 3, 1, 1, False), (256, 256, 3, 1, 1, False))
@@ -55,7 +55,7 @@ def repack_conv_weight(w: Tensor) -> Tensor:
     """torch's [cout, cin, kh, kw] as the [K, cout] array the convolution reads, K = kh * kw * cin in the order (kh, kw, cin)."""
     cout, cin, kh, kw = w.shape
     if w.is_cuda:
-        src = _as_f32(w)
+        src = as_f32(w)
         out = torch.empty(kh * kw * cin, cout, dtype=torch.float32, device=w.device)
         call("mtgs_lpips_repack", cout, cin, kh, kw, ptr(src), ptr(out), stream_of(src))
         return out
@@ -136,7 +136,7 @@ def _check_nhwc(x: Tensor) -> Tensor:
     if x.dim() != 4 or x.shape[0] < 1:
         raise ValueError(f"activations must be [n, h, w, c], got {tuple(x.shape)}")
     require_gpu(x)
-    return _as_f32(x)
+    return as_f32(x)
 
 
 def conv2d_nhwc(x: Tensor, packed: Tensor, bias: Tensor, kernel: int, stride: int, pad: int, relu: bool = True) -> Tensor:
@@ -158,7 +158,7 @@ def conv2d_nhwc(x: Tensor, packed: Tensor, bias: Tensor, kernel: int, stride: in
 def conv_first(pred: Tensor, gt: Tensor, mask: Optional[Tensor], packed: Tensor, bias: Tensor, *, normalize: bool = True,
                kernel: int = 11, stride: int = 4, pad: int = 2, relu: bool = True) -> Tensor:
     """The first layer's form of lpips_conv alone: the input transform applied on load."""
-    pred_c, gt_c, mask_c = _images(pred, gt, mask)
+    pred_c, gt_c, mask_c = image_pair(pred, gt, mask, metric="lpips")
     H, W = pred_c.shape[:2]
     cout = packed.shape[1]
     if cout % 32 != 0:
@@ -179,51 +179,25 @@ def maxpool_nhwc(x: Tensor) -> Tensor:
     return out
 
 
-def _images(pred: Tensor, gt: Tensor, mask: Optional[Tensor]):
-    if pred.dim() != 3:
-        raise ValueError(f"pred must be [H, W, C], got {tuple(pred.shape)}")
-    if pred.shape[-1] != 3:
-        raise NotImplementedError(f"pred has {pred.shape[-1]} channels: only 3-channel images are implemented")
-    if pred.shape != gt.shape:
-        raise ValueError(f"pred {tuple(pred.shape)} and gt {tuple(gt.shape)} must have the same shape")
-    if torch.is_grad_enabled() and (pred.requires_grad or gt.requires_grad):
-        raise RuntimeError("lpips is a metric here, forward only: an input requires grad (detach it or call under torch.no_grad())")
-    H, W = pred.shape[:2]
-    if mask is not None and mask.numel() != H * W:
-        raise ValueError(f"mask must have H * W = {H * W} elements, got {tuple(mask.shape)}")
-    require_gpu(pred, gt, mask)
-    return _as_f32(pred), _as_f32(gt), _mask_u8(mask, H, W)
-
-
-_workspaces: dict = {}      # (H, W, device) -> uint8 tensor
-
-
-def _workspace(H: int, W: int, device) -> Tensor:
-    key = (H, W, device)
-    ws = _workspaces.get(key)
-    if ws is None:
-        ws = _workspaces[key] = torch.empty(size_query("mtgs_lpips_workspace_bytes", H, W), dtype=torch.uint8, device=device)
-    return ws
-
-
 def lpips(pred: Tensor, gt: Tensor, mask: Optional[Tensor] = None, *, weights: LpipsWeights, normalize: bool = True,
           norm: str = "torchmetrics") -> Tensor:
     """LPIPS (AlexNet) of pred * mask and gt * mask, [H, W, 3] images in [0, 1] (normalize=True) or [-1, 1] (False), the mask
     [H, W, 1] or [H, W] bool or uint8 (non-zero keeps the pixel).  Returns a 0-dim fp32 tensor on the images' device.
     [RECALL] norm: "torchmetrics" (the default; x / sqrt(1e-8 + sum x^2), recalled, not checked against torchmetrics here) or
-    "lpips" (x / (sqrt(sum x^2) + 1e-10), the original package's).  The workspace is kept per (H, W, device)."""
+    "lpips" (x / (sqrt(sum x^2) + 1e-10), the original package's).  The workspace is kept per (device, stream, H, W)."""
     if norm not in NORMS:
         raise ValueError(f"norm must be one of {sorted(NORMS)}, got {norm!r}")
-    pred_c, gt_c, mask_c = _images(pred, gt, mask)
+    pred_c, gt_c, mask_c = image_pair(pred, gt, mask, metric="lpips")
     H, W = pred_c.shape[:2]
     if H < MIN_SIDE or W < MIN_SIDE:
         raise ValueError(f"a {H} x {W} image leaves no pixel after the second pool: both sides must be >= {MIN_SIDE}")
     if weights.device != pred_c.device:
         raise RuntimeError(f"weights are on {weights.device}, the images on {pred_c.device}: move them once with weights.to(device)")
-    ws = _workspace(H, W, pred_c.device)
+    stream = stream_of(pred_c)
+    ws = scratch(("lpips", H, W), lambda: size_query("mtgs_lpips_workspace_bytes", H, W), pred_c.device, stream)
     out = torch.empty((), dtype=torch.float32, device=pred_c.device)
     call("mtgs_lpips", H, W, ptr(pred_c), ptr(gt_c), ptr(mask_c), ptr(weights.flat), int(normalize), NORMS[norm], ptr(out), ptr(ws),
-         ws.numel(), stream_of(pred_c))
+         ws.numel(), stream)
     return out
 
 

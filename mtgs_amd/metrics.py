@@ -17,21 +17,12 @@ from typing import Dict, Optional
 import torch
 from torch import Tensor
 
+from ._inputs import as_f32, image_pair
 from ._lib import call, ptr, require_gpu, stream_of, workspace
-from .loss import _as_f32, _mask_u8
 from .dino import DinoWeights, dino_similarity
 from .lpips import LpipsWeights, lpips
 
 _EPS = 0.5 / 255
-
-
-def _check_images(a: Tensor, b: Tensor, names) -> None:
-    if a.dim() != 3:
-        raise ValueError(f"{names[0]} must be [H, W, C], got {tuple(a.shape)}")
-    if a.shape[-1] != 3:
-        raise NotImplementedError(f"{names[0]} has {a.shape[-1]} channels: only 3-channel images are implemented")
-    if a.shape != b.shape:
-        raise ValueError(f"{names[0]} {tuple(a.shape)} and {names[1]} {tuple(b.shape)} must have the same shape")
 
 
 def _workspace(P: int, num_iters: int, dev) -> Tensor:
@@ -41,17 +32,15 @@ def _workspace(P: int, num_iters: int, dev) -> Tensor:
 def color_correct(img: Tensor, ref: Tensor, mask: Optional[Tensor] = None, num_iters: int = 5, eps: float = _EPS) -> Tensor:
     """The reference's color_correct(img * mask, ref * mask) (or color_correct(img, ref) without a mask) on [H, W, 3] images.
     If any fit is singular (a Cholesky pivot <= 1e-12 of its diagonal entry) or not finite, returns img * mask unchanged."""
-    _check_images(img, ref, ("img", "ref"))
     if num_iters < 0:
         raise ValueError(f"num_iters must be >= 0, got {num_iters}")
-    require_gpu(img, ref, mask)
-    img_c, ref_c = _as_f32(img), _as_f32(ref)
+    img_c, ref_c, mask_c = image_pair(img, ref, mask, ("img", "ref"))
     H, W = img_c.shape[:2]
     out = torch.empty_like(img_c)
     if H * W == 0:
         return out
     ws = _workspace(H * W, num_iters, img_c.device)
-    call("mtgs_color_correct", H * W, int(num_iters), float(eps), ptr(img_c), ptr(ref_c), ptr(_mask_u8(mask, H, W)), ptr(out),
+    call("mtgs_color_correct", H * W, int(num_iters), float(eps), ptr(img_c), ptr(ref_c), ptr(mask_c), ptr(out),
          ptr(ws), ws.numel(), stream_of(img_c))
     return out
 
@@ -65,25 +54,24 @@ def image_metrics(pred: Tensor, gt: Tensor, mask: Optional[Tensor] = None, *, co
     with 0.1 < lidar < 80 and the mask.  Empty selections give nan, a zero error gives inf (as torch).
     lpips (lpips_weights given) = lpips(pred, gt, mask, weights=lpips_weights), LPIPS(normalize=True) of gt * mask and pred * mask.
     dinov2_sim (dino_weights given) = dino_similarity(pred, gt, mask, weights=dino_weights), DINOv2Similarity.similarity(pred, gt, mask)."""
-    _check_images(pred, gt, ("pred", "gt"))
     if (pred_depth is None) != (lidar_depth is None):
         raise ValueError("pred_depth and lidar_depth must be given together")
-    require_gpu(pred, gt, mask, pred_depth, lidar_depth)
-    pred_c, gt_c = _as_f32(pred), _as_f32(gt)
+    pred_c, gt_c, mask_c = image_pair(pred, gt, mask)
+    require_gpu(pred_depth, lidar_depth)
     H, W = pred_c.shape[:2]
     P = H * W
     depths = None
     if pred_depth is not None:
         if pred_depth.numel() != P or lidar_depth.numel() != P:
             raise ValueError(f"depths must have H * W = {P} elements, got {pred_depth.numel()} and {lidar_depth.numel()}")
-        depths = (_as_f32(pred_depth, H, W), _as_f32(lidar_depth, H, W))
+        depths = (as_f32(pred_depth, H, W), as_f32(lidar_depth, H, W))
     num_iters = 5 if color_corrected else 0
     if P == 0:
         out = torch.full((5,), float("nan"), dtype=torch.float32, device=pred_c.device)
     else:
         out = torch.empty(5, dtype=torch.float32, device=pred_c.device)
         ws = _workspace(P, num_iters, pred_c.device)
-        call("mtgs_image_metrics", P, num_iters, _EPS, ptr(pred_c), ptr(gt_c), ptr(_mask_u8(mask, H, W)),
+        call("mtgs_image_metrics", P, num_iters, _EPS, ptr(pred_c), ptr(gt_c), ptr(mask_c),
              ptr(depths[0]) if depths else None, ptr(depths[1]) if depths else None, ptr(out), ptr(ws), ws.numel(), stream_of(pred_c))
     res = {"psnr": out[0]}
     if color_corrected:

@@ -14,8 +14,8 @@ from typing import Dict, Optional
 import torch
 from torch import Tensor
 
+from ._inputs import point_rows, row_stride
 from ._lib import call, ptr, require_gpu, stream_of, workspace
-from .seed import _points
 
 MIN_NB_NEIGHBORS, MAX_NB_NEIGHBORS = 2, 32
 _AXES = "xyz"
@@ -30,7 +30,7 @@ def statistical_outlier_removal(points: Tensor, nb_neighbors: int = 20, std_rati
     With return_stats also (avg [N] float64, {"cloud_mean", "std", "threshold", "valid"} as a float64 tensor [4]).
     Raises ValueError on non-finite coordinates."""
     require_gpu(points)
-    p = _points(points)
+    p = point_rows(points)
     N, nb = p.shape[0], int(nb_neighbors)
     if not MIN_NB_NEIGHBORS <= nb <= MAX_NB_NEIGHBORS:
         raise ValueError(f"nb_neighbors must be in [{MIN_NB_NEIGHBORS}, {MAX_NB_NEIGHBORS}], got {nb}")
@@ -41,7 +41,7 @@ def statistical_outlier_removal(points: Tensor, nb_neighbors: int = 20, std_rati
     if N > 0:
         status = torch.empty(1, dtype=torch.int32, device=dev)
         ws = workspace("mtgs_cloud_outlier_workspace_bytes", N, nb, device=dev, dtype=torch.uint8)
-        call("mtgs_cloud_outlier", N, nb, float(std_ratio), ptr(p), p.stride(0) if N > 1 else 3, ptr(avg), ptr(stats), ptr(keep),
+        call("mtgs_cloud_outlier", N, nb, float(std_ratio), ptr(p), row_stride(p), ptr(avg), ptr(stats), ptr(keep),
              ptr(status), ptr(ws), ws.numel(), stream_of(p))
         if int(status.item()) != 0:
             raise ValueError("Input contains NaN or infinity: statistical_outlier_removal needs finite coordinates")
@@ -59,7 +59,7 @@ def voxel_down_sample(points: Tensor, colors: Tensor, voxel_size: float, return_
     int64.  One host synchronisation (M).  Raises ValueError on non-finite coordinates and when the extent of an axis needs
     more than 2^21 voxels."""
     require_gpu(points, colors)
-    p = _points(points)
+    p = point_rows(points)
     N, dev = p.shape[0], p.device
     vs = float(voxel_size)
     if not (vs > 0.0 and vs != float("inf")):
@@ -78,7 +78,7 @@ def voxel_down_sample(points: Tensor, colors: Tensor, voxel_size: float, return_
     if N > 0:
         ctl = torch.empty(2, dtype=torch.int32, device=dev)             # n_voxels, status: read together
         ws = workspace("mtgs_cloud_voxel_workspace_bytes", N, device=dev, dtype=torch.uint8)
-        call("mtgs_cloud_voxel", N, vs, ptr(p), p.stride(0) if N > 1 else 3, ptr(c), int(c.dtype == torch.uint8), ptr(xyz), ptr(rgb),
+        call("mtgs_cloud_voxel", N, vs, ptr(p), row_stride(p), ptr(c), int(c.dtype == torch.uint8), ptr(xyz), ptr(rgb),
              ptr(counts), ptr(keys), ctl.data_ptr(), ctl.data_ptr() + 4, ptr(ws), ws.numel(), stream_of(p))
         M, status = (int(v) for v in ctl.tolist())
         if status & 1:

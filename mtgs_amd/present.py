@@ -31,10 +31,11 @@ import torch
 from torch import Tensor
 
 from . import _abi
-from ._lib import PRESENT_HEADER, call, ptr, require_gpu, stream_of
+from ._inputs import shape_of
+from ._lib import call, ptr, require_gpu, scratch, stream_of
 from .jpeg import JpegStream, encode_jpeg
 
-_ABI = _abi.header_abi(PRESENT_HEADER)
+_ABI = _abi.header_abi("mtgs_present.h")
 _PANEL = _ABI.structs["mtgs_present_panel"]
 MAX_PANELS = _ABI.constants["MTGS_PRESENT_MAX_PANELS"]
 _RGB, _FLOAT, _DEPTH, _BOOL = (_ABI.constants["MTGS_PRESENT_" + k] for k in ("RGB", "FLOAT", "DEPTH", "BOOL"))
@@ -163,7 +164,7 @@ class _Source:
 def _source(image: Tensor, options: ColormapOptions, name: str) -> _Source:
     """apply_colormap's dispatch on the channel count and dtype"""
     if not isinstance(image, Tensor) or image.dim() != 3:
-        raise ValueError(f"{name} must be a [H, W, C] tensor, got {tuple(image.shape) if isinstance(image, Tensor) else type(image).__name__}")
+        raise ValueError(f"{name} must be a [H, W, C] tensor, got {shape_of(image)}")
     if not image.is_contiguous():
         raise ValueError(f"{name} must be contiguous (shape {tuple(image.shape)}, strides {image.stride()})")
     if image.shape[0] < 1 or image.shape[1] < 1:
@@ -190,17 +191,6 @@ def _depth_source(depth: Tensor, accumulation, near, far, options, name="depth")
         if accumulation.dtype != torch.float32 or tuple(accumulation.shape) != tuple(depth.shape) or not accumulation.is_contiguous():
             raise ValueError(f"accumulation must be contiguous float32 {tuple(depth.shape)}, got {accumulation.dtype} {tuple(accumulation.shape)}")
     return _Source(depth, _DEPTH, options, accumulation, None if near is None else float(near), None if far is None else float(far))
-
-
-_WORKSPACES: Dict[Tuple[torch.device, int], Tensor] = {}
-
-
-def _workspace(device, stream) -> Tensor:
-    """the 16 KB of partial extrema, one per (device, stream): allocated once, so that a frame with `out=` allocates nothing"""
-    key = (device, stream)
-    if key not in _WORKSPACES:
-        _WORKSPACES[key] = torch.empty(_WS_BYTES, dtype=torch.uint8, device=device)
-    return _WORKSPACES[key]
 
 
 def _compose(sources: Sequence[_Source], places, out_h: int, out_w: int, split_column: int, fmt: int, out: Optional[Tensor]) -> Tensor:
@@ -236,7 +226,8 @@ def _compose(sources: Sequence[_Source], places, out_h: int, out_w: int, split_c
     stream = stream_of(first)
     if out is None:
         out = torch.empty((out_h, out_w, 3), dtype=dtype, device=first.device)
-    ws = _workspace(first.device, stream) if needs_stats else None
+    # the 16 KB of partial extrema, one per (device, stream): allocated once, so that a frame with `out=` allocates nothing
+    ws = scratch(("present",), _WS_BYTES, first.device, stream) if needs_stats else None
     panels = table.ctypes.data_as(C.c_void_p)
     if needs_stats:
         call("mtgs_present_stats", len(sources), panels, ptr(ws), ws.numel(), stream)

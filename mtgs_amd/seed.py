@@ -15,6 +15,7 @@ from typing import Dict, Mapping, Optional
 import torch
 from torch import Tensor
 
+from ._inputs import point_rows, row_stride
 from ._lib import call, ptr, require_gpu, stream_of, workspace
 
 MAX_K = 8
@@ -25,25 +26,13 @@ def num_sh_bases(degree: int) -> int:
     return (degree + 1) ** 2 if 0 <= degree <= 3 else 25
 
 
-def _points(points: Tensor) -> Tensor:
-    """float32 rows whose three coordinates are contiguous; the row stride is kept (a [N, 4][:, :3] view is read in place)"""
-    if points.dim() != 2 or points.shape[1] != 3:
-        raise ValueError(f"points must be [N, 3], got {tuple(points.shape)}")
-    p = points.detach()
-    if p.dtype != torch.float32:
-        p = p.to(torch.float32)
-    if p.shape[0] > 1 and (p.stride(1) != 1 or p.stride(0) < 3):
-        p = p.contiguous()
-    return p
-
-
 def knn_distances(points: Tensor, k: int = 3, return_indices: bool = False):
     """Distances [N, k] (float32, ascending) from every point to its k nearest OTHER points: sklearn's
     NearestNeighbors(n_neighbors=k + 1, metric="euclidean").kneighbors(points) without the first column.  Exact; duplicates give
     exact zeros; bitwise reproducible.  With return_indices also their indices [N, k] int64 (the smaller index first among equal
     distances).  Raises ValueError on non-finite coordinates and when N <= k, as sklearn does."""
     require_gpu(points)
-    p = _points(points)
+    p = point_rows(points)
     N, k = p.shape[0], int(k)
     if not 1 <= k <= MAX_K:
         raise ValueError(f"k must be in [1, {MAX_K}], got {k}")
@@ -54,7 +43,7 @@ def knn_distances(points: Tensor, k: int = 3, return_indices: bool = False):
     idx = torch.empty((N, k), dtype=torch.int32, device=dev) if return_indices else None
     status = torch.empty(1, dtype=torch.int32, device=dev)
     ws = workspace("mtgs_knn_workspace_bytes", N, k, device=dev, dtype=torch.uint8)
-    call("mtgs_knn", N, k, ptr(p), p.stride(0) if N > 1 else 3, ptr(dist), ptr(idx), ptr(status), ptr(ws), ws.numel(), stream_of(p))
+    call("mtgs_knn", N, k, ptr(p), row_stride(p), ptr(dist), ptr(idx), ptr(status), ptr(ws), ws.numel(), stream_of(p))
     if int(status.item()) != 0:
         raise ValueError("Input contains NaN or infinity: knn_distances needs finite coordinates")
     return (dist, idx.to(torch.int64)) if return_indices else dist

@@ -133,7 +133,7 @@ def main():
     lines = [f"mtgs_amd.dino_similarity (ViT-B/14 at {S} x {S}: {d} wide, {cfg.heads} heads, {cfg.depth} blocks, {T} tokens per image) against the "
              f"torch.nn.functional chain, {torch.cuda.get_device_name(0)}, torch {torch.__version__}",
              f"device events around one call, median (min .. max) of {a.reps} after {a.warmup} warm-ups; seeded random weights; "
-             f"workspace {D._workspace(cfg, torch.device('cuda', torch.cuda.current_device())).numel() / 1e6:.1f} MB", ""]
+             f"workspace {D.workspace_bytes(cfg) / 1e6:.1f} MB", ""]
 
     def say(*new):
         lines.extend(new)

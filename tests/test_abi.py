@@ -59,6 +59,54 @@ def test_prototypes_match_the_frozen_signatures():
     assert signatures["mtgs_rast_last_error"] == ("s", "")
 
 
+def included_headers():
+    from mtgs_amd import _abi
+    return _abi.included_headers()
+
+
+@pytest.mark.parametrize("header", included_headers())
+def test_an_included_header_is_declared_bound_and_exported(hip_lib, header):
+    """Every header that mtgs_rast.h includes is a group of entry points of its own: read by mtgs_amd._abi.header_abi, bound by
+    mtgs_amd._lib (GROUPS), exported by the library, with a reviewed record tests/golden/abi_signatures_<x>.txt in the spelling of
+    abi_signatures.txt.  The groups are additive: the ABI versions stay 29 and 7."""
+    from mtgs_amd import _abi, _lib
+    abi = _abi.header_abi(header)
+    frozen = (ROOT / "tests" / "golden" / f"abi_signatures_{header[len('mtgs_'):-len('.h')]}.txt").read_text()
+    assert "".join(f"{name}({args}) {res}\n" for name, (res, args) in sorted(abi.signatures.items())) == frozen
+    assert re.search(r'^#include "%s"' % re.escape(header), (ROOT / "include" / "mtgs_rast.h").read_text(), re.M)
+    text = re.sub(r"/\*.*?\*/", "", (ROOT / "include" / header).read_text(), flags=re.S)
+    names = sorted(set(re.findall(r"\b(mtgs_[a-z0-9_]+)\s*\(", text)))
+    assert names == sorted(abi.signatures) == sorted(_lib.GROUPS[header]) and names
+    raw = C.CDLL(str(_lib.LIB_PATH))
+    for name, (restype, argtypes) in abi.prototypes.items():
+        assert hasattr(raw, name), f"{name} not exported by libmtgs_rast.so"
+        fn = getattr(hip_lib, name)
+        assert fn.restype is C.c_int is restype and list(fn.argtypes) == argtypes
+    assert abi.prototypes == {name: (LETTERS[res], [LETTERS[a] for a in args]) for name, (res, args) in abi.signatures.items()}
+    assert _abi.constant("MTGS_RAST_ABI_VERSION") == 29 == header_define("MTGS_RAST_ABI_VERSION")
+    assert _abi.constant("MTGS_RAST_HOT_ABI_VERSION") == 7 == header_define("MTGS_RAST_HOT_ABI_VERSION")
+    assert hip_lib.mtgs_rast_version() == 29 and hip_lib.mtgs_rast_hot_version() == 7
+
+
+def test_the_groups_are_the_headers_the_records_and_disjoint():
+    """One table: the header files, the #include lines and the reviewed records name the same groups; no entry point belongs to two
+    groups, the main header's own declarations included; a header that is not included is refused by name."""
+    from mtgs_amd import _abi, _lib
+    files = {p.name for p in (ROOT / "include").glob("mtgs_*.h")} - {"mtgs_rast.h"}
+    records = {"mtgs_" + p.stem[len("abi_signatures_"):] + ".h" for p in (ROOT / "tests" / "golden").glob("abi_signatures_*.txt")}
+    included = _abi.included_headers()
+    assert files == set(included) == records and len(set(included)) == len(included)
+    assert list(_lib.GROUPS) == ["mtgs_rast.h", *included] and _lib.GROUPS["mtgs_rast.h"] is _lib.EXPORTS
+    assert sorted(_lib.EXPORTS) == sorted(_abi.signatures()) == header_symbols()
+    groups = list(_lib.GROUPS.items())
+    for i, (a, names_a) in enumerate(groups):
+        assert len(set(names_a)) == len(names_a), a
+        for b, names_b in groups[i + 1:]:
+            assert not set(names_a) & set(names_b), (a, b)
+    with pytest.raises(ValueError, match="does not include"):
+        _abi.header_abi("mtgs_nothing.h")
+
+
 @pytest.mark.parametrize("text, names", [
     ("int mtgs_ok(int n);\nint mtgs_bad(long n, void *stream);\n", r"line 2.*'long'.*mtgs_bad"),                # an unknown type
     ("typedef struct mtgs_s {\n    int64_t n;\n\n    int flag : 3;\n} mtgs_s;\n", r"line 4.*mtgs_s.*'int flag : 3'"),   # a bit-field

@@ -3,7 +3,6 @@ preprocessing against Pillow's recorded output (tests/golden/dino_preprocess.npz
 host-built tables against the restatement, the crop and nearest rules, the weight handling and its refusals, and the header as a
 group of its own."""
 import ctypes as C
-import re
 from pathlib import Path
 
 import numpy as np
@@ -179,29 +178,15 @@ def test_the_reference_discriminates():
 
 
 # ---- the C ABI -------------------------------------------------------------------------------------------------------------------
-def test_the_header_is_declared_bound_and_exported(hip_lib):
-    """include/mtgs_dino.h is included by mtgs_rast.h, read by mtgs_amd._abi.header_abi and bound by mtgs_amd._lib as a group of its
-    own (DINO_EXPORTS).  Its reviewed record is tests/golden/abi_signatures_dino.txt.  Additive: the ABI versions stay 29 and 7."""
+def test_the_header_is_declared_bound_and_exported():
+    """include/mtgs_dino.h is a group of its own (tests/test_abi.py checks every group against its header, its reviewed record
+    tests/golden/abi_signatures_dino.txt and the library): its entry points, its configuration record and its constants."""
     from mtgs_amd import _abi, _lib
     abi = _abi.header_abi("mtgs_dino.h")
-    frozen = (ROOT / "tests" / "golden" / "abi_signatures_dino.txt").read_text()
-    assert "".join(f"{name}({args}) {res}\n" for name, (res, args) in sorted(abi.signatures.items())) == frozen
-    assert sorted(abi.signatures) == NAMES == sorted(_lib.DINO_EXPORTS)
-    assert re.search(r'^#include "mtgs_dino\.h"', (ROOT / "include" / "mtgs_rast.h").read_text(), re.M)
-    assert "mtgs_dino.h" not in _abi.EXTENSION_HEADERS
-    assert not set(NAMES) & (set(_lib.EXPORTS) | set(_lib.EXTENSION_EXPORTS) | set(_lib.REFINE_SCENE_EXPORTS) | set(_lib.PRESENT_EXPORTS) | set(_lib.LPIPS_EXPORTS))
-    text = re.sub(r"/\*.*?\*/", "", (ROOT / "include" / "mtgs_dino.h").read_text(), flags=re.S)
-    assert sorted(set(re.findall(r"\b(mtgs_dino_[a-z0-9_]+)\s*\(", text))) == NAMES
-    raw = C.CDLL(str(_lib.LIB_PATH))
-    for name, (restype, argtypes) in abi.prototypes.items():
-        assert hasattr(raw, name), f"{name} not exported by libmtgs_rast.so"
-        fn = getattr(hip_lib, name)
-        assert fn.restype is C.c_int is restype and list(fn.argtypes) == argtypes
+    assert sorted(_lib.GROUPS["mtgs_dino.h"]) == NAMES
     assert abi.structs["mtgs_dino_config"].names == ("dim", "heads", "depth", "patch", "image", "mlp_ratio", "ln_eps") and abi.structs["mtgs_dino_config"].itemsize == 28
     assert [abi.constants[k] for k in ("MTGS_DINO_EPI_BIAS", "MTGS_DINO_EPI_BIAS_GELU", "MTGS_DINO_EPI_SCALE_RESIDUAL", "MTGS_DINO_EPI_PATCH_EMBED")] == [0, 1, 2, 3]
     assert (abi.constants["MTGS_DINO_PATCH"], abi.constants["MTGS_DINO_HEAD_DIM"], abi.constants["MTGS_DINO_MAX_DIM"]) == (14, 64, 1024) == (D.PATCH, D.HEAD_DIM, D.MAX_DIM)
-    assert _abi.constant("MTGS_RAST_ABI_VERSION") == 29 and _abi.constant("MTGS_RAST_HOT_ABI_VERSION") == 7
-    assert hip_lib.mtgs_rast_version() == 29 and hip_lib.mtgs_rast_hot_version() == 7
 
 
 def test_the_size_queries_need_no_device(hip_lib):

@@ -206,6 +206,18 @@ def test_voxel_grid_boundaries_float_colours_and_corners():
     assert [tuple(t.shape) for t in pointcloud.voxel_down_sample(*e, 0.15)] == [(0, 3), (0, 3), (0,)]
 
 
+def test_voxel_grid_reads_a_column_strided_view_of_one_row_as_its_copy():
+    """points = wide[:1, ::2]: one row has no row stride to tell the layout by, and the coordinates are two elements apart; read in
+    place the voxel's mean would be (x, 50, y).  The backing row holds six elements."""
+    wide = torch.full((1, 6), 50.0, device=DEV)
+    wide[:, ::2] = torch.tensor([[1.25, -2.5, 3.75]], device=DEV)
+    view, colors = wide[:, ::2], torch.tensor([[10, 20, 30]], dtype=torch.uint8, device=DEV)
+    assert view.stride(1) == 2 and tuple(view.shape) == (1, 3)
+    got, want = (pointcloud.voxel_down_sample(p, colors, 0.15, return_keys=True) for p in (view, view.contiguous()))
+    assert all(torch.equal(a, b) for a, b in zip(got, want))
+    assert got[0].tolist() == [[1.25, -2.5, 3.75]] and got[2].tolist() == [1]
+
+
 def test_voxel_grid_refuses_an_extent_beyond_21_bits():
     x = street(4096).copy()
     x[5, 1] = 4e5                                                 # 4e5 / 0.15 = 2.7e6 voxels along y

@@ -7,6 +7,7 @@ import pytest
 import torch
 
 from mtgs_amd import crop
+from mtgs_amd._inputs import point_rows
 from mtgs_amd.crop import OrientedBox, crop_gaussians
 from tests import crop_refs as R
 from tests.util import small_scene
@@ -72,7 +73,7 @@ def test_select_reads_a_strided_view_in_place(lib, N):
     wide = torch.full((N, 4), float("nan"), device=DEV)
     wide[:, :3] = torch.tensor(pts, device=DEV)
     view = wide[:, :3]
-    assert N == 1 or crop._points(view).data_ptr() == wide.data_ptr() and crop._points(view).stride(0) == 4
+    assert N == 1 or point_rows(view).data_ptr() == wide.data_ptr() and point_rows(view).stride(0) == 4
     a, b = select(view, box), select(view.contiguous(), box)
     for x, y in zip(a, b):
         assert np.array_equal(x, y)

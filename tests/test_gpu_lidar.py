@@ -295,6 +295,34 @@ def test_strides_and_dtypes():
     check_depth(p32, E32, K32, W, H, what="float32 matrices")
 
 
+@pytest.mark.parametrize("dtype", [np.float32, np.float64], ids=["float32", "float64"])
+@pytest.mark.parametrize("n", [1, 2])
+def test_a_column_strided_view_of_one_row_is_read_as_its_copy(n, dtype):
+    """points = wide[:, ::2]: the coordinates are two elements apart.  One such row has no row stride to tell it by (torch reports any
+    stride for a single row) and must be copied like two; read in place, (x, 50, y) lies outside every camera.  The backing rows hold
+    six elements, so nothing is read outside the allocation either way.  Bitwise against the contiguous copy, and the restatement."""
+    w, h = 32, 16
+    points = np.array([[10.0, 0.5, 0.2], [8.0, -1.0, -0.3]], dtype=dtype)[:n]
+    cams = [R.camera(yaw, 20.0, (0.0, 0.0, 0.0), w, h) for yaw in (0.0, 5.0)]
+    mats, (_, E, K) = np.stack([c[0] for c in cams]), cams[0]
+    images, masks = textures(2, w, h)
+
+    def view(a):
+        wide = torch.full((len(a), 6), 50.0, dtype=torch.from_numpy(a).dtype, device="cuda")
+        wide[:, ::2] = dev(a)
+        return wide[:, ::2]
+
+    v = view(points)
+    assert v.stride(1) == 2 and v.shape == (n, 3) and not v.is_contiguous() and torch.equal(v, dev(points))
+    depth, index = L.depth_image(v, dev(E), dev(K), w, h, return_index=True)
+    depth_c, index_c = L.depth_image(v.contiguous(), dev(E), dev(K), w, h, return_index=True)
+    assert torch.equal(depth, depth_c) and torch.equal(index, index_c) and int((index >= 0).sum()) == n
+    painted, painted_c = (L.paint_points(p, dev(mats), dev(images), dev(masks)) for p in (v, v.contiguous()))
+    assert all(torch.equal(a, b) for a, b in zip(painted, painted_c)) and painted.count.tolist() == [2] * n
+    check_depth(points, E, K, w, h, what=f"one column-strided view, N={n}", make=view)
+    check_paint(points, mats, images, masks, what=f"one column-strided view, N={n}", make=view)
+
+
 # ---- channel order and partial inputs -------------------------------------------------------------------------------------------------
 def test_channel_order_and_partial_inputs():
     pts = R.sweep(np.random.default_rng(13), 900)

@@ -175,6 +175,33 @@ def test_identical_images_give_exactly_zero_and_calls_repeat_bitwise():
     assert lpips(2 * pred - 1, 2 * gt - 1, None, weights=dev, normalize=False).item() > 0
 
 
+def test_the_scratch_is_per_stream():
+    """The metric on the default stream and on two others, one call at a time: the results are bitwise equal, and each stream has a
+    scratch tensor of its own (mtgs_amd._lib.scratch keys on the stream), allocated once."""
+    from mtgs_amd import _lib
+    from mtgs_amd.lpips import lpips
+    _, _, dev = _weights()
+    pred, gt, mask = (t.cuda() for t in R.images(31, 31, seed=4, masked=True))
+    torch.cuda.synchronize()
+    results, scratches = [], []
+
+    def run(stream):
+        with torch.cuda.stream(stream):
+            out = lpips(pred, gt, mask, weights=dev)
+        torch.cuda.synchronize()
+        results.append(out.view(torch.int32).item())
+        scratches.append(_lib.scratch(("lpips", 31, 31), lambda: pytest.fail("the call left no scratch for its stream"), pred.device, stream.cuda_stream))
+
+    a, b = torch.cuda.Stream(), torch.cuda.Stream()
+    for stream in (torch.cuda.current_stream(), a, b):
+        run(stream)
+    assert results[0] == results[1] == results[2]
+    assert len({t.data_ptr() for t in scratches}) == 3 and all(t.numel() > 0 and t.dtype == torch.uint8 for t in scratches)
+    entries = len(_lib._scratch)
+    run(a)
+    assert scratches[3] is scratches[1] and len(_lib._scratch) == entries and results[3] == results[0]
+
+
 def test_image_metrics_gains_the_key_and_keeps_the_others():
     from mtgs_amd import image_metrics
     from mtgs_amd.metrics import lpips

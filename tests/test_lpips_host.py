@@ -1,8 +1,6 @@
 """LPIPS (mtgs_amd/lpips.py, csrc/lpips.hip, include/mtgs_lpips.h) without a GPU: the header as a group of its own, the fp64
 restatement's own properties (tests/lpips_refs.py), the tap-size arithmetic, and the weight handling (order, counts, repack)."""
 import ctypes as C
-import re
-from pathlib import Path
 
 import pytest
 import torch
@@ -10,7 +8,6 @@ import torch
 from mtgs_amd import lpips as L
 from tests import lpips_refs as R
 
-ROOT = Path(__file__).resolve().parents[1]
 NAMES = ["mtgs_lpips", "mtgs_lpips_conv", "mtgs_lpips_conv_first", "mtgs_lpips_maxpool", "mtgs_lpips_repack", "mtgs_lpips_weight_floats",
          "mtgs_lpips_workspace_bytes"]
 
@@ -21,28 +18,14 @@ def weights():
 
 
 # ---- the C ABI -------------------------------------------------------------------------------------------------------------------
-def test_the_header_is_declared_bound_and_exported(hip_lib):
-    """include/mtgs_lpips.h is included by mtgs_rast.h, read by mtgs_amd._abi.header_abi and bound by mtgs_amd._lib as a group of its
-    own (LPIPS_EXPORTS).  Its reviewed record is tests/golden/abi_signatures_lpips.txt.  Additive: the ABI versions stay 29 and 7."""
+def test_the_header_is_declared_bound_and_exported():
+    """include/mtgs_lpips.h is a group of its own (tests/test_abi.py checks every group against its header, its reviewed record
+    tests/golden/abi_signatures_lpips.txt and the library): its entry points and its constants."""
     from mtgs_amd import _abi, _lib
     abi = _abi.header_abi("mtgs_lpips.h")
-    frozen = (ROOT / "tests" / "golden" / "abi_signatures_lpips.txt").read_text()
-    assert "".join(f"{name}({args}) {res}\n" for name, (res, args) in sorted(abi.signatures.items())) == frozen
-    assert sorted(abi.signatures) == NAMES == sorted(_lib.LPIPS_EXPORTS)
-    assert re.search(r'^#include "mtgs_lpips\.h"', (ROOT / "include" / "mtgs_rast.h").read_text(), re.M)
-    assert "mtgs_lpips.h" not in _abi.EXTENSION_HEADERS
-    assert not set(NAMES) & (set(_lib.EXPORTS) | set(_lib.EXTENSION_EXPORTS) | set(_lib.REFINE_SCENE_EXPORTS) | set(_lib.PRESENT_EXPORTS))
-    text = re.sub(r"/\*.*?\*/", "", (ROOT / "include" / "mtgs_lpips.h").read_text(), flags=re.S)
-    assert sorted(set(re.findall(r"\b(mtgs_[a-z0-9_]+)\s*\(", text))) == NAMES
-    raw = C.CDLL(str(_lib.LIB_PATH))
-    for name, (restype, argtypes) in abi.prototypes.items():
-        assert hasattr(raw, name), f"{name} not exported by libmtgs_rast.so"
-        fn = getattr(hip_lib, name)
-        assert fn.restype is C.c_int is restype and list(fn.argtypes) == argtypes
+    assert sorted(_lib.GROUPS["mtgs_lpips.h"]) == NAMES
     assert [abi.constants[k] for k in ("MTGS_LPIPS_NORM_SQRT_EPS_INSIDE", "MTGS_LPIPS_NORM_EPS_OUTSIDE")] == [L.NORMS["torchmetrics"], L.NORMS["lpips"]]
     assert abi.constants["MTGS_LPIPS_MIN_SIDE"] == L.MIN_SIDE == 31
-    assert _abi.constant("MTGS_RAST_ABI_VERSION") == 29 and _abi.constant("MTGS_RAST_HOT_ABI_VERSION") == 7
-    assert hip_lib.mtgs_rast_version() == 29 and hip_lib.mtgs_rast_hot_version() == 7
 
 
 def test_the_size_queries_need_no_device(hip_lib):

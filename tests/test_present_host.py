@@ -3,8 +3,6 @@ own, the layout arithmetic against hand-worked cases, the two references of test
 what the Python layer refuses before it touches a device, and the host-side checks of the C entry points."""
 import ctypes as C
 import math
-import re
-from pathlib import Path
 
 import numpy as np
 import pytest
@@ -13,31 +11,16 @@ import torch
 from mtgs_amd import present as P
 from tests import present_refs as R
 
-ROOT = Path(__file__).resolve().parents[1]
 NAMES = ["mtgs_present_compose", "mtgs_present_depth_resize", "mtgs_present_stats", "mtgs_present_workspace_bytes"]
 
 
 # ---- the C ABI -------------------------------------------------------------------------------------------------------------------
 def test_the_header_is_declared_bound_and_exported(hip_lib):
-    """include/mtgs_present.h is included by mtgs_rast.h, read by mtgs_amd._abi.header_abi and bound by mtgs_amd._lib as a group of
-    its own (PRESENT_EXPORTS): it joins neither mtgs_rast.h's record, nor the extension headers', nor the refinement's.  Its
-    reviewed record is tests/golden/abi_signatures_present.txt.  Additive: the ABI versions stay 29 and 7."""
+    """include/mtgs_present.h is a group of its own (tests/test_abi.py checks every group against its header, its reviewed record
+    tests/golden/abi_signatures_present.txt and the library): its entry points, its panel record and its constants."""
     from mtgs_amd import _abi, _lib
     abi = _abi.header_abi("mtgs_present.h")
-    frozen = (ROOT / "tests" / "golden" / "abi_signatures_present.txt").read_text()
-    assert "".join(f"{name}({args}) {res}\n" for name, (res, args) in sorted(abi.signatures.items())) == frozen
-    assert sorted(abi.signatures) == NAMES == sorted(_lib.PRESENT_EXPORTS)
-    main = (ROOT / "include" / "mtgs_rast.h").read_text()
-    assert re.search(r'^#include "mtgs_present\.h"', main, re.M)
-    assert "mtgs_present.h" not in _abi.EXTENSION_HEADERS
-    assert not set(NAMES) & (set(_lib.EXPORTS) | set(_lib.EXTENSION_EXPORTS) | set(_lib.REFINE_SCENE_EXPORTS))
-    text = re.sub(r"/\*.*?\*/", "", (ROOT / "include" / "mtgs_present.h").read_text(), flags=re.S)
-    assert sorted(set(re.findall(r"\b(mtgs_[a-z0-9_]+)\s*\(", text))) == NAMES
-    raw = C.CDLL(str(_lib.LIB_PATH))
-    for name, (restype, argtypes) in abi.prototypes.items():
-        assert hasattr(raw, name), f"{name} not exported by libmtgs_rast.so"
-        fn = getattr(hip_lib, name)
-        assert fn.restype is C.c_int is restype and list(fn.argtypes) == argtypes
+    assert sorted(_lib.GROUPS["mtgs_present.h"]) == NAMES
     # the panel record the Python layer fills is the header's struct, of the size the library reports
     ws, pb = C.c_size_t(0), C.c_size_t(0)
     assert hip_lib.mtgs_present_workspace_bytes(C.byref(ws), C.byref(pb)) == 0
@@ -45,8 +28,6 @@ def test_the_header_is_declared_bound_and_exported(hip_lib):
     assert ws.value == P._WS_BYTES == 8 * 256 * 2 * 4
     assert P.MAX_PANELS == abi.constants["MTGS_PRESENT_MAX_PANELS"] == 8
     assert [abi.constants["MTGS_PRESENT_" + k] for k in ("RGB", "FLOAT", "DEPTH", "BOOL")] == [0, 1, 2, 3]
-    assert _abi.constant("MTGS_RAST_ABI_VERSION") == 29 and _abi.constant("MTGS_RAST_HOT_ABI_VERSION") == 7
-    assert hip_lib.mtgs_rast_version() == 29 and hip_lib.mtgs_rast_hot_version() == 7
 
 
 # ---- layout arithmetic -------------------------------------------------------------------------------------------------------------

@@ -3,7 +3,6 @@ with oracle/refine_oracle.py where the two overlap, the seeded scenes of tests/t
 from its threshold, the sky case separates the two cull rules, the C entry points of include/mtgs_refine_scene.h are declared,
 bound, exported and refuse bad arguments by name, and refine_scene refuses what it does not support before it touches a device."""
 import ctypes as C
-import re
 from pathlib import Path
 
 import numpy as np
@@ -118,35 +117,17 @@ NAMES = ["mtgs_refine_scene_apply", "mtgs_refine_scene_classify", "mtgs_refine_s
 
 
 def test_the_header_is_declared_bound_and_exported(hip_lib):
-    """include/mtgs_refine_scene.h is included by mtgs_rast.h, read by mtgs_amd._abi.header_abi and bound by mtgs_amd._lib as a
-    group of its own: it joins neither mtgs_rast.h's own record nor the extension headers'.  Its reviewed record is
-    tests/golden/abi_signatures_refine_scene.txt.  The ABI version is 29: the one that removed the single-node entry points."""
+    """include/mtgs_refine_scene.h is a group of its own (tests/test_abi.py checks every group against its header, its reviewed
+    record tests/golden/abi_signatures_refine_scene.txt and the library): its entry points, its two tables and its constants."""
     from mtgs_amd import _abi, _lib, densify
     abi = _abi.header_abi("mtgs_refine_scene.h")
-    frozen = (ROOT / "tests" / "golden" / "abi_signatures_refine_scene.txt").read_text()
-    assert "".join(f"{name}({args}) {res}\n" for name, (res, args) in sorted(abi.signatures.items())) == frozen
-    assert sorted(abi.signatures) == NAMES == sorted(_lib.REFINE_SCENE_EXPORTS)
-    main = (ROOT / "include" / "mtgs_rast.h").read_text()
-    assert re.search(r'^#include "mtgs_refine_scene\.h"', main, re.M)
-    assert not set(NAMES) & set(_abi.signatures()) and not set(NAMES) & set(_abi.extension_signatures())
-    assert "mtgs_refine_scene.h" not in _abi.EXTENSION_HEADERS and not set(NAMES) & (set(_lib.EXPORTS) | set(_lib.EXTENSION_EXPORTS))
-    text = re.sub(r"/\*.*?\*/", "", (ROOT / "include" / "mtgs_refine_scene.h").read_text(), flags=re.S)
-    assert sorted(set(re.findall(r"\b(mtgs_[a-z0-9_]+)\s*\(", text))) == NAMES
-    with pytest.raises(ValueError, match="does not include"):
-        _abi.header_abi("mtgs_nothing.h")
-    raw = C.CDLL(str(_lib.LIB_PATH))
-    for name, (restype, argtypes) in abi.prototypes.items():
-        assert hasattr(raw, name), f"{name} not exported by libmtgs_rast.so"
-        fn = getattr(hip_lib, name)
-        assert fn.restype is C.c_int is restype and list(fn.argtypes) == argtypes
+    assert sorted(_lib.GROUPS["mtgs_refine_scene.h"]) == NAMES
     # the two tables: the record dtypes the Python layer uploads are the header's structs, of the size the library reports
     nb, mb = C.c_size_t(0), C.c_size_t(0)
     assert hip_lib.mtgs_refine_scene_table_bytes(C.byref(nb), C.byref(mb)) == 0
     assert (nb.value, mb.value) == (densify._REFINE_NODE.itemsize, densify._REFINE_MOVE.itemsize) == (264, 64)
     assert densify._REFINE_NODE == abi.structs["mtgs_refine_node"] and densify._REFINE_MOVE == abi.structs["mtgs_refine_move"]
     assert abi.constants["MTGS_REFINE_MAX_COLUMNS"] == 6 and (abi.constants["MTGS_REFINE_DENSIFY"], abi.constants["MTGS_REFINE_CULL_ONLY"]) == (1, 2)
-    assert _abi.constant("MTGS_RAST_ABI_VERSION") == 29 and _abi.constant("MTGS_RAST_HOT_ABI_VERSION") == 7
-    assert hip_lib.mtgs_rast_version() == 29 and hip_lib.mtgs_rast_hot_version() == 7
 
 
 def test_the_c_compiler_lays_the_tables_out_as_the_reader_does(tmp_path):

@@ -153,8 +153,9 @@ def test_config2_config3_1080p_forward_backward(gs, oracle, N, sh):
 
 @pytest.mark.parametrize("W,H", [(1280, 720), (960, 540), (333, 211)])
 def test_midsize_images_use_more_waves_per_tile(gs, oracle, W, H):
-    """Image sizes that select 2 or 4 waves per tile (fewer than 6144 / 3072 tiles forward, 4096 / 1536
-    backward; MTGS trains at 960x540): same parity bars as the one-wave-per-tile configuration."""
+    """Image sizes that select 2 or 4 waves per tile (pick_ppl of blend.hip: fewer than 16000 / 3000 tiles forward,
+    6000 / 1536 backward, the four-wave backward with at most 4 channels only; MTGS trains at 960x540): same parity
+    bars as the one-wave-per-tile configuration."""
     N = 200_000
     sc = make_scene(N, seed=4)
     vm, K = make_camera(W, H, yaw_deg=30.0)

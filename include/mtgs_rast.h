@@ -40,6 +40,7 @@
 #include "mtgs_dino.h"   /* a block of its own: the DINOv2 similarity metric: Pillow's resample, a ViT forward on f32 MFMA, the cosine tail */
 #include "mtgs_jpeg.h"   /* a block of its own: presented frames as baseline JPEG, byte for byte libjpeg's integer path */
 #include "mtgs_lidar.h"   /* a block of its own: lidar sweeps through the cameras: the sparse depth image, the cloud's colours and labels */
+#include "mtgs_frame.h"   /* a block of its own: training frames at a stage's resolution: Pillow's BILINEAR and NEAREST resize, the masks */
 
 #ifdef __cplusplus
 extern "C" {

@@ -68,3 +68,30 @@ def image_pair(pred: Tensor, gt: Tensor, mask: Optional[Tensor], names=("pred", 
         raise ValueError(f"mask must have H * W = {H * W} elements, got {tuple(mask.shape)}")
     require_gpu(pred, gt, mask)
     return as_f32(pred), as_f32(gt), mask_u8(mask, H, W)
+
+
+def image_plane(x, name: str, dtypes, channels=(1, 2, 3)):
+    """(view [H, W, C] of `x` in its own strides, whether `x` came as [H, W]) of one plane of a frame: a tensor [H, W] or [H, W, C]
+    of one of `dtypes` with at least one pixel.  Nothing is copied: the frame kernels take any strides."""
+    if not isinstance(x, Tensor) or x.dim() not in (2, 3):
+        raise ValueError(f"{name} must be [H, W] or [H, W, C], got {shape_of(x)}")
+    if x.dtype not in dtypes:
+        raise TypeError(f"{name} must be {' or '.join(str(d).removeprefix('torch.') for d in dtypes)}, got {x.dtype}")
+    flat = x.dim() == 2
+    v = x.detach()
+    v = v.unsqueeze(-1) if flat else v
+    if v.shape[2] not in channels:
+        raise NotImplementedError(f"{name} has {v.shape[2]} channels: only {', '.join(map(str, channels))} are implemented")
+    if v.shape[0] < 1 or v.shape[1] < 1:
+        raise ValueError(f"{name} must have at least one pixel, got {tuple(x.shape)}")
+    return v, flat
+
+
+def image_size(size, name: str = "size"):
+    """(height, width) of a target size: two integers of at least 1"""
+    ok = isinstance(size, (tuple, list)) and len(size) == 2 and all(isinstance(v, int) and not isinstance(v, bool) for v in size)
+    if not ok:
+        raise ValueError(f"{name} must be (height, width), two integers, got {size!r}")
+    if size[0] < 1 or size[1] < 1:
+        raise ValueError(f"{name} must be at least 1 x 1, got {tuple(size)}")
+    return int(size[0]), int(size[1])

@@ -36,9 +36,12 @@ COMMON_FLAGS = [
 # jpeg.hip (the JPEG encoder) is integer arithmetic; its one fp32 conversion uses __fmul_rn / __fadd_rn, which never fuse.
 # lidar.hip (the lidar depth image, the cloud's colours and labels) is fp64 whose products and sums round separately: its discrete
 # outputs (pixels, field of view, labels) are compared bit for bit with a NumPy restatement.
+# frame.hip (Pillow's resize of a training frame) adds (double)float * double products in double, tap by tap, as Pillow's C does: a
+# fused multiply-add would skip the product's rounding and change bits of the float32 depth.
 PER_FILE_FLAGS = {"project.hip": ["-ffp-contract=off"], "front.hip": ["-ffp-contract=off"], "metrics.hip": ["-ffp-contract=off"],
                   "geomloss.hip": ["-ffp-contract=off"], "depthloss.hip": ["-ffp-contract=off"], "seed.hip": ["-ffp-contract=off"], "cloud.hip": ["-ffp-contract=off"],
-                  "crop.hip": ["-ffp-contract=off"], "present.hip": ["-ffp-contract=off"], "lidar.hip": ["-ffp-contract=off"]}
+                  "crop.hip": ["-ffp-contract=off"], "present.hip": ["-ffp-contract=off"], "lidar.hip": ["-ffp-contract=off"],
+                  "frame.hip": ["-ffp-contract=off"]}
 
 
 class HipccNotFound(RuntimeError):

@@ -231,16 +231,16 @@ def crop_offset(size: int, S: int) -> int:
     return int(round((size - S) / 2.0))
 
 
-def bilinear_coefficients(in_size: int, out_size: int, first: int, count: int):
-    """Pillow's precompute_coeffs + normalize_coeffs_8bpc for the BILINEAR filter, outputs first .. first + count - 1:
-    (bounds [count, 2] int32 = (xmin, taps), coefficients [count, ksize] int32)."""
+def bilinear_weights(in_size: int, out_size: int, first: int, count: int):
+    """Pillow's precompute_coeffs for the BILINEAR filter, outputs first .. first + count - 1: (bounds [count, 2] int32 =
+    (xmin, taps), weights [count, ksize] float64), the normalised double weights its 32-bit ("F") resampling multiplies by."""
     scale = in_size / out_size
     fs = max(scale, 1.0)
     support = 1.0 * fs
     ss = 1.0 / fs
     ksize = int(np.ceil(support)) * 2 + 1
     bounds = np.zeros((count, 2), np.int32)
-    coef = np.zeros((count, ksize), np.int32)
+    weights = np.zeros((count, ksize), np.float64)
     for j in range(count):
         center = (first + j + 0.5) * scale
         xmin = max(int(center - support + 0.5), 0)
@@ -252,9 +252,19 @@ def bilinear_coefficients(in_size: int, out_size: int, first: int, count: int):
         if ww != 0.0:
             w = w / ww
         bounds[j] = (xmin, xmax)
-        coef[j, :xmax] = [int(0.5 + v * (1 << PRECISION_BITS)) for v in w]
+        weights[j, :xmax] = w
     taps = max(1, int(bounds[:, 1].max()))
-    return bounds, np.ascontiguousarray(coef[:, :taps])
+    return bounds, np.ascontiguousarray(weights[:, :taps])
+
+
+def bilinear_coefficients(in_size: int, out_size: int, first: int, count: int):
+    """Pillow's precompute_coeffs + normalize_coeffs_8bpc for the BILINEAR filter, outputs first .. first + count - 1:
+    (bounds [count, 2] int32 = (xmin, taps), coefficients [count, ksize] int32)."""
+    bounds, weights = bilinear_weights(in_size, out_size, first, count)
+    coef = np.zeros(weights.shape, np.int32)
+    for j in range(count):                     # int(0.5 + w * 2^22): the weights are >= 0, so the truncation is a floor
+        coef[j, :bounds[j, 1]] = [int(0.5 + v * (1 << PRECISION_BITS)) for v in weights[j, :bounds[j, 1]]]
+    return bounds, coef
 
 
 def nearest_sources(in_size: int, out_size: int, first: int, count: int) -> np.ndarray:
@@ -469,5 +479,5 @@ def dino_similarity(pred: Tensor, gt: Tensor, mask: Optional[Tensor] = None, *, 
 
 
 __all__ = ["DinoConfig", "DinoWeights", "dino_preprocess", "dino_patch_weights", "dino_linear", "dino_layernorm", "dino_attention", "dino_features",
-           "dino_tail", "dino_similarity", "resample_tables", "resized_size", "crop_offset", "bilinear_coefficients", "nearest_sources", "PATCH",
+           "dino_tail", "dino_similarity", "resample_tables", "resized_size", "crop_offset", "bilinear_weights", "bilinear_coefficients", "nearest_sources", "PATCH",
            "HEAD_DIM", "MAX_DIM", "EPILOGUES"]

@@ -22,7 +22,9 @@ metric of get_metrics_dict, AlexNet on f32 MFMA: `LpipsWeights`, `mtgs_amd.metri
 Pillow's: `encode_jpeg`, `JpegStream`, `viewer_frame(..., jpeg_quality=)`, `render_frame(..., jpeg_quality=)`), `mtgs_amd.lidar` (lidar
 sweeps through the cameras: the sparse lidar depth image of a frame and the colours and labels of the seeding cloud -- `depth_image`,
 `paint_points`, `PaintedPoints`), `mtgs_amd.frame` (a training frame at its scale stage's resolution, byte for byte Pillow's BILINEAR and
-NEAREST resize, and the masks of a frame: `resize_plane`, `resize_frame`, `frame_masks`, `masked_labels`, `scaled_size`).
+NEAREST resize, and the masks of a frame: `resize_plane`, `resize_frame`, `frame_masks`, `masked_labels`, `scaled_size`), `mtgs_amd.stack` (the lidar sweeps of a traversal
+split by the annotated boxes, painted and stacked into the background cloud and one cloud per tracked object: `split_sweep`,
+`box_matrices`, `SweepStack`, `StackedClouds`).
 """
 from .appearance import wild_color_source, wild_colors
 from .crop import OrientedBox, crop_gaussians
@@ -37,6 +39,7 @@ from .present import ColormapOptions, colorize, colorize_depth, render_frame, vi
 from .pointcloud import prepare_seed_cloud, statistical_outlier_removal, voxel_down_sample
 from .rendering import rasterization
 from .seed import knn_distances, seed_gaussians, sky_points
+from .stack import SplitSweep, StackedClouds, SweepStack, box_matrices, split_sweep
 from .wrapper import (exact_lists, fully_fused_projection, graph_mode, isect_offset_encode, isect_tiles, lists_are_tight,
                       rasterize_to_pixels, sh_lazy, sh_prefill, spherical_harmonics, tight_lists)
 
@@ -47,4 +50,5 @@ __all__ = ["rasterization", "spherical_harmonics", "fully_fused_projection", "is
            "statistical_outlier_removal", "voxel_down_sample", "prepare_seed_cloud", "OrientedBox", "crop_gaussians", "refine_scene", "NodeRefine", "RefineConfig",
            "ColormapOptions", "colorize", "colorize_depth", "viewer_frame", "viewer_depth", "render_frame", "LpipsWeights",
            "DinoConfig", "DinoWeights", "dino_similarity", "JpegStream", "encode_jpeg", "depth_image", "paint_points", "PaintedPoints",
-           "resize_plane", "resize_frame", "frame_masks", "masked_labels", "scaled_size"]
+           "resize_plane", "resize_frame", "frame_masks", "masked_labels", "scaled_size",
+           "split_sweep", "box_matrices", "SweepStack", "SplitSweep", "StackedClouds"]

@@ -38,10 +38,12 @@ COMMON_FLAGS = [
 # outputs (pixels, field of view, labels) are compared bit for bit with a NumPy restatement.
 # frame.hip (Pillow's resize of a training frame) adds (double)float * double products in double, tap by tap, as Pillow's C does: a
 # fused multiply-add would skip the product's rounding and change bits of the float32 depth.
+# stack.hip (lidar sweeps split by the boxes and stacked) is fp64 like lidar.hip: the owner of a point is decided by <= on sums of
+# products, and its box-frame and global coordinates are compared bit for bit with a NumPy restatement.
 PER_FILE_FLAGS = {"project.hip": ["-ffp-contract=off"], "front.hip": ["-ffp-contract=off"], "metrics.hip": ["-ffp-contract=off"],
                   "geomloss.hip": ["-ffp-contract=off"], "depthloss.hip": ["-ffp-contract=off"], "seed.hip": ["-ffp-contract=off"], "cloud.hip": ["-ffp-contract=off"],
                   "crop.hip": ["-ffp-contract=off"], "present.hip": ["-ffp-contract=off"], "lidar.hip": ["-ffp-contract=off"],
-                  "frame.hip": ["-ffp-contract=off"]}
+                  "frame.hip": ["-ffp-contract=off"], "stack.hip": ["-ffp-contract=off"]}
 
 
 class HipccNotFound(RuntimeError):

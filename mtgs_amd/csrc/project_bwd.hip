@@ -175,9 +175,11 @@ __global__ __launch_bounds__(PROJ_BLOCK) void project_bwd_kernel(
     const int32_t *__restrict__ row_index, const ProjExpand ex) {
     __shared__ float red[(PROJ_BLOCK / 64) * 12];
     __shared__ float s_acc[PROJ_MAX_CAMS * 12];
+    __shared__ float s_over[12];  // block sum of ONE camera c >= PROJ_MAX_CAMS: flushed and cleared at once (thread k owns [k])
     __shared__ int s_list[PROJ_BLOCK];
     __shared__ int s_wcnt[PROJ_BLOCK / 64];
     for (int k = threadIdx.x; k < PROJ_MAX_CAMS * 12; k += PROJ_BLOCK) s_acc[k] = 0.f;
+    if (threadIdx.x < 12) s_over[threadIdx.x] = 0.f;
     for (int64_t chunk = (int64_t)blockIdx.x * PROJ_BLOCK; chunk < N; chunk += (int64_t)gridDim.x * PROJ_BLOCK) {
     __syncthreads();  // s_list / s_wcnt / red reuse, s_acc initialisation
     // Only ~15 % of the Gaussians are visible and they are scattered over the index range: one thread
@@ -261,11 +263,14 @@ __global__ __launch_bounds__(PROJ_BLOCK) void project_bwd_kernel(
         }
         if (v_viewmats) {
             __syncthreads();
-            block_reduce_viewmat(vRt, s_acc + (c % PROJ_MAX_CAMS) * 12, red);
-            if (c >= PROJ_MAX_CAMS && threadIdx.x < 12) {  // (not reached by MTGS) flush immediately
+            // cameras beyond the LDS slots (not reached by MTGS) go through a slot of their own: the slots of s_acc hold the
+            // sums of cameras 0 .. PROJ_MAX_CAMS - 1 until the end of the kernel and must not be shared
+            block_reduce_viewmat(vRt, c < PROJ_MAX_CAMS ? s_acc + c * 12 : s_over, red);
+            if (c >= PROJ_MAX_CAMS && threadIdx.x < 12) {  // flush immediately
                 const int k = threadIdx.x;
-                atomicAdd(v_viewmats + c * 16 + (k < 9 ? (k / 3) * 4 + (k % 3) : (k - 9) * 4 + 3), s_acc[(c % PROJ_MAX_CAMS) * 12 + k]);
-                s_acc[(c % PROJ_MAX_CAMS) * 12 + k] = 0.f;
+                const float v = s_over[k];
+                if (v != 0.f) atomicAdd(v_viewmats + (int64_t)c * 16 + (k < 9 ? (k / 3) * 4 + (k % 3) : (k - 9) * 4 + 3), v);
+                s_over[k] = 0.f;
             }
         }
     }

@@ -42,6 +42,7 @@
 #include "mtgs_lidar.h"   /* a block of its own: lidar sweeps through the cameras: the sparse depth image, the cloud's colours and labels */
 #include "mtgs_frame.h"   /* a block of its own: training frames at a stage's resolution: Pillow's BILINEAR and NEAREST resize, the masks */
 #include "mtgs_stack.h"   /* a block of its own: lidar sweeps split by the boxes, painted and stacked into background and object clouds */
+#include "mtgs_jpegdec.h"   /* a block of its own: baseline JPEG frames decoded on the device, byte for byte as Pillow decodes them */
 
 #ifdef __cplusplus
 extern "C" {

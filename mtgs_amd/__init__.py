@@ -19,7 +19,8 @@ depth: `ColormapOptions`, `colorize`, `colorize_depth`, `viewer_frame`, `viewer_
 metric of get_metrics_dict, AlexNet on f32 MFMA: `LpipsWeights`, `mtgs_amd.metrics.lpips`, `image_metrics(..., lpips_weights=)`),
 `mtgs_amd.dino` (the DINOv2 similarity metric, dinov2_sim: Pillow's resize and a ViT forward on the device -- `DinoConfig`, `DinoWeights`,
 `dino_similarity`, `image_metrics(..., dino_weights=)`), `mtgs_amd.jpeg` (the presented frame as a baseline JPEG file, byte for byte
-Pillow's: `encode_jpeg`, `JpegStream`, `viewer_frame(..., jpeg_quality=)`, `render_frame(..., jpeg_quality=)`), `mtgs_amd.lidar` (lidar
+Pillow's: `encode_jpeg`, `JpegStream`, `viewer_frame(..., jpeg_quality=)`, `render_frame(..., jpeg_quality=)`), `mtgs_amd.jpegdec` (a baseline JPEG
+file decoded on the device, byte for byte Pillow's pixels: `parse_jpeg`, `upload_jpeg`, `decode_jpeg`, `DeviceJpeg`, `JpegInfo`), `mtgs_amd.lidar` (lidar
 sweeps through the cameras: the sparse lidar depth image of a frame and the colours and labels of the seeding cloud -- `depth_image`,
 `paint_points`, `PaintedPoints`), `mtgs_amd.frame` (a training frame at its scale stage's resolution, byte for byte Pillow's BILINEAR and
 NEAREST resize, and the masks of a frame: `resize_plane`, `resize_frame`, `frame_masks`, `masked_labels`, `scaled_size`), `mtgs_amd.stack` (the lidar sweeps of a traversal
@@ -32,6 +33,7 @@ from .densify import NodeRefine, RefineConfig, refine_scene
 from .dino import DinoConfig, DinoWeights, dino_similarity
 from .frame import frame_masks, masked_labels, resize_frame, resize_plane, scaled_size
 from .jpeg import JpegStream, encode_jpeg
+from .jpegdec import DeviceJpeg, JpegInfo, decode_jpeg, parse_jpeg, upload_jpeg
 from .lidar import PaintedPoints, depth_image, paint_points
 from .lpips import LpipsWeights
 from .metrics import color_correct, image_metrics
@@ -49,6 +51,6 @@ __all__ = ["rasterization", "spherical_harmonics", "fully_fused_projection", "is
            "wild_colors", "wild_color_source", "color_correct", "image_metrics", "knn_distances", "seed_gaussians", "sky_points",
            "statistical_outlier_removal", "voxel_down_sample", "prepare_seed_cloud", "OrientedBox", "crop_gaussians", "refine_scene", "NodeRefine", "RefineConfig",
            "ColormapOptions", "colorize", "colorize_depth", "viewer_frame", "viewer_depth", "render_frame", "LpipsWeights",
-           "DinoConfig", "DinoWeights", "dino_similarity", "JpegStream", "encode_jpeg", "depth_image", "paint_points", "PaintedPoints",
+           "DinoConfig", "DinoWeights", "dino_similarity", "JpegStream", "encode_jpeg", "DeviceJpeg", "JpegInfo", "decode_jpeg", "parse_jpeg", "upload_jpeg", "depth_image", "paint_points", "PaintedPoints",
            "resize_plane", "resize_frame", "frame_masks", "masked_labels", "scaled_size",
            "split_sweep", "box_matrices", "SweepStack", "SplitSweep", "StackedClouds"]

@@ -20,6 +20,7 @@
 // of the block count, so no kernel's addresses depend on the pixels beyond that bound: MTGS_JPEG_BLOCK_BITS per block holds because
 // the categories are clamped to what 8-bit samples can reach (11 for a DC difference, 10 for an AC coefficient).
 #include "common.hpp"
+#include "jpeg_zigzag.hpp"
 #include "scan.hpp"
 
 namespace {
@@ -33,9 +34,6 @@ constexpr int PACK_WAVES = 4;
 constexpr int DQT0_AT = 2 + 18 + 5, DQT1_AT = DQT0_AT + 69;   // the 64 entries of table 0 and of table 1 inside the header
 
 // ---- tables: ITU-T T.81 Annex K ------------------------------------------------------------------------------------------------------
-#define MTGS_JPEG_ZIGZAG                                                                                                          \
-    0, 1, 8, 16, 9, 2, 3, 10, 17, 24, 32, 25, 18, 11, 4, 5, 12, 19, 26, 33, 40, 48, 41, 34, 27, 20, 13, 6, 7, 14, 21, 28, 35, 42, 49, \
-        56, 57, 50, 43, 36, 29, 22, 15, 23, 30, 37, 44, 51, 58, 59, 52, 45, 38, 31, 39, 46, 53, 60, 61, 54, 47, 55, 62, 63
 constexpr uint8_t ZIGZAG[64] = {MTGS_JPEG_ZIGZAG};
 __constant__ uint8_t c_zigzag[64] = {MTGS_JPEG_ZIGZAG};
 

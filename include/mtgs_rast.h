@@ -43,6 +43,7 @@
 #include "mtgs_frame.h"   /* a block of its own: training frames at a stage's resolution: Pillow's BILINEAR and NEAREST resize, the masks */
 #include "mtgs_stack.h"   /* a block of its own: lidar sweeps split by the boxes, painted and stacked into background and object clouds */
 #include "mtgs_jpegdec.h"   /* a block of its own: baseline JPEG frames decoded on the device, byte for byte as Pillow decodes them */
+#include "mtgs_icp.h"   /* a block of its own: lidar sweeps registered across traversals: down-sampling, the voxel map, the ICP iteration */
 
 #ifdef __cplusplus
 extern "C" {

@@ -25,7 +25,9 @@ sweeps through the cameras: the sparse lidar depth image of a frame and the colo
 `paint_points`, `PaintedPoints`), `mtgs_amd.frame` (a training frame at its scale stage's resolution, byte for byte Pillow's BILINEAR and
 NEAREST resize, and the masks of a frame: `resize_plane`, `resize_frame`, `frame_masks`, `masked_labels`, `scaled_size`), `mtgs_amd.stack` (the lidar sweeps of a traversal
 split by the annotated boxes, painted and stacked into the background cloud and one cloud per tracked object: `split_sweep`,
-`box_matrices`, `SweepStack`, `StackedClouds`).
+`box_matrices`, `SweepStack`, `StackedClouds`), `mtgs_amd.registration` (the lidar sweeps of all traversals registered against a local
+voxel map, KISS-ICP in a canonical order: `KissConfig`, `VoxelMap`, `LidarOdometry`, `register_traversals`, `align_points_to_map`,
+`align_poses`, `registration_errors`).
 """
 from .appearance import wild_color_source, wild_colors
 from .crop import OrientedBox, crop_gaussians
@@ -39,6 +41,8 @@ from .lpips import LpipsWeights
 from .metrics import color_correct, image_metrics
 from .present import ColormapOptions, colorize, colorize_depth, render_frame, viewer_depth, viewer_frame
 from .pointcloud import prepare_seed_cloud, statistical_outlier_removal, voxel_down_sample
+from .registration import (KissConfig, LidarOdometry, VoxelMap, align_points_to_map, align_poses, register_traversals,
+                           registration_errors)
 from .rendering import rasterization
 from .seed import knn_distances, seed_gaussians, sky_points
 from .stack import SplitSweep, StackedClouds, SweepStack, box_matrices, split_sweep
@@ -53,4 +57,5 @@ __all__ = ["rasterization", "spherical_harmonics", "fully_fused_projection", "is
            "ColormapOptions", "colorize", "colorize_depth", "viewer_frame", "viewer_depth", "render_frame", "LpipsWeights",
            "DinoConfig", "DinoWeights", "dino_similarity", "JpegStream", "encode_jpeg", "DeviceJpeg", "JpegInfo", "decode_jpeg", "parse_jpeg", "upload_jpeg", "depth_image", "paint_points", "PaintedPoints",
            "resize_plane", "resize_frame", "frame_masks", "masked_labels", "scaled_size",
-           "split_sweep", "box_matrices", "SweepStack", "SplitSweep", "StackedClouds"]
+           "split_sweep", "box_matrices", "SweepStack", "SplitSweep", "StackedClouds",
+           "KissConfig", "VoxelMap", "LidarOdometry", "register_traversals", "align_points_to_map", "align_poses", "registration_errors"]

@@ -40,10 +40,12 @@ COMMON_FLAGS = [
 # fused multiply-add would skip the product's rounding and change bits of the float32 depth.
 # stack.hip (lidar sweeps split by the boxes and stacked) is fp64 like lidar.hip: the owner of a point is decided by <= on sums of
 # products, and its box-frame and global coordinates are compared bit for bit with a NumPy restatement.
+# icp.hip (lidar registration) is fp64 in a stated order: voxel indices, the map's accept / refuse rule, the nearest neighbour and the
+# 27 sums of an iteration are compared bit for bit with a NumPy restatement.
 PER_FILE_FLAGS = {"project.hip": ["-ffp-contract=off"], "front.hip": ["-ffp-contract=off"], "metrics.hip": ["-ffp-contract=off"],
                   "geomloss.hip": ["-ffp-contract=off"], "depthloss.hip": ["-ffp-contract=off"], "seed.hip": ["-ffp-contract=off"], "cloud.hip": ["-ffp-contract=off"],
                   "crop.hip": ["-ffp-contract=off"], "present.hip": ["-ffp-contract=off"], "lidar.hip": ["-ffp-contract=off"],
-                  "frame.hip": ["-ffp-contract=off"], "stack.hip": ["-ffp-contract=off"]}
+                  "frame.hip": ["-ffp-contract=off"], "stack.hip": ["-ffp-contract=off"], "icp.hip": ["-ffp-contract=off"]}
 
 
 class HipccNotFound(RuntimeError):

@@ -44,6 +44,7 @@
 #include "mtgs_stack.h"   /* a block of its own: lidar sweeps split by the boxes, painted and stacked into background and object clouds */
 #include "mtgs_jpegdec.h"   /* a block of its own: baseline JPEG frames decoded on the device, byte for byte as Pillow decodes them */
 #include "mtgs_icp.h"   /* a block of its own: lidar sweeps registered across traversals: down-sampling, the voxel map, the ICP iteration */
+#include "mtgs_undistort.h"   /* a block of its own: lens undistortion of a training frame: the fp64 map, 8-bit linear and nearest remap, the valid mask */
 
 #ifdef __cplusplus
 extern "C" {

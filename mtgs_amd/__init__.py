@@ -27,7 +27,9 @@ NEAREST resize, and the masks of a frame: `resize_plane`, `resize_frame`, `frame
 split by the annotated boxes, painted and stacked into the background cloud and one cloud per tracked object: `split_sweep`,
 `box_matrices`, `SweepStack`, `StackedClouds`), `mtgs_amd.registration` (the lidar sweeps of all traversals registered against a local
 voxel map, KISS-ICP in a canonical order: `KissConfig`, `VoxelMap`, `LidarOdometry`, `register_traversals`, `align_points_to_map`,
-`align_poses`, `registration_errors`).
+`align_poses`, `registration_errors`), `mtgs_amd.undistort` (the lens undistortion of a training frame, one launch for every plane, by
+a rule the project defines: `optimal_new_camera_matrix`, `undistort_camera`, `undistort_plane`, `undistort_frame`, `undistort_map`,
+`UndistortCamera`).
 """
 from .appearance import wild_color_source, wild_colors
 from .crop import OrientedBox, crop_gaussians
@@ -45,6 +47,8 @@ from .registration import (KissConfig, LidarOdometry, VoxelMap, align_points_to_
                            registration_errors)
 from .rendering import rasterization
 from .seed import knn_distances, seed_gaussians, sky_points
+from .undistort import (UndistortCamera, optimal_new_camera_matrix, undistort_camera, undistort_frame, undistort_map,
+                        undistort_plane)
 from .stack import SplitSweep, StackedClouds, SweepStack, box_matrices, split_sweep
 from .wrapper import (exact_lists, fully_fused_projection, graph_mode, isect_offset_encode, isect_tiles, lists_are_tight,
                       rasterize_to_pixels, sh_lazy, sh_prefill, spherical_harmonics, tight_lists)
@@ -58,4 +62,5 @@ __all__ = ["rasterization", "spherical_harmonics", "fully_fused_projection", "is
            "DinoConfig", "DinoWeights", "dino_similarity", "JpegStream", "encode_jpeg", "DeviceJpeg", "JpegInfo", "decode_jpeg", "parse_jpeg", "upload_jpeg", "depth_image", "paint_points", "PaintedPoints",
            "resize_plane", "resize_frame", "frame_masks", "masked_labels", "scaled_size",
            "split_sweep", "box_matrices", "SweepStack", "SplitSweep", "StackedClouds",
-           "KissConfig", "VoxelMap", "LidarOdometry", "register_traversals", "align_points_to_map", "align_poses", "registration_errors"]
+           "KissConfig", "VoxelMap", "LidarOdometry", "register_traversals", "align_points_to_map", "align_poses", "registration_errors",
+           "UndistortCamera", "optimal_new_camera_matrix", "undistort_camera", "undistort_plane", "undistort_frame", "undistort_map"]

@@ -19,8 +19,9 @@ call; the kernels take matrices, never boxes.  A frame reads nothing back and ca
 `finish` makes one host read, of the totals that size its outputs.  All arithmetic is fp64 in the stated order; tests/stack_refs.py
 restates it in NumPy.
 
-Out of scope: parsing the .pcd sweeps and the `only_top` selection, undistortion and `adjust_brightness` (OpenCV), and writing the
-.pcd files: the caller hands in the sweep and the undistorted images and takes device tensors back.
+Out of scope: parsing the .pcd sweeps and the `only_top` selection, `adjust_brightness` (OpenCV), and writing the .pcd files: the
+caller hands in the sweep and the undistorted images and takes device tensors back.  The undistortion itself (mode
+keep_focal_length, linear for the images, nearest for the masks) is mtgs_amd.undistort.undistort_plane, by a rule the project defines.
 """
 from __future__ import annotations
 

@@ -14,7 +14,7 @@ extern "C" {
  * tests/golden/abi_signatures_frame.txt.  Additive: it changed neither MTGS_RAST_ABI_VERSION nor MTGS_RAST_HOT_ABI_VERSION.
  * Conventions (device pointers, `stream`, return codes, mtgs_rast_last_error) are mtgs_rast.h's.  Covered: Pillow's BILINEAR
  * resampling of 8-bit and of float32 ("F") images, its NEAREST resampling, and the masks of NumPy's rules below.  NOT covered:
- * adjust_brightness, decoding the depth PNG, RGBA (Pillow premultiplies it around the resize); cv2.remap undistortion is mtgs_undistort.h.
+ * decoding the depth PNG, RGBA (Pillow premultiplies it around the resize); cv2.remap undistortion is mtgs_undistort.h, adjust_brightness mtgs_brightness.h.
  *
  * Tables.  Every resampler reads HOST-built tables that live on the device (mtgs_amd.frame builds and keeps them per shape).
  *   bounds[n_out][2] int32 = (first source index, taps) of one axis; coef[n_out][ksize] its taps' coefficients, ksize >= every

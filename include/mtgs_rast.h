@@ -45,6 +45,7 @@
 #include "mtgs_jpegdec.h"   /* a block of its own: baseline JPEG frames decoded on the device, byte for byte as Pillow decodes them */
 #include "mtgs_icp.h"   /* a block of its own: lidar sweeps registered across traversals: down-sampling, the voxel map, the ICP iteration */
 #include "mtgs_undistort.h"   /* a block of its own: lens undistortion of a training frame: the fp64 map, 8-bit linear and nearest remap, the valid mask */
+#include "mtgs_brightness.h"  /* a block of its own: camera brightness equalisation: the 8-bit HSV adjust of V and the per-camera factors from the lidar overlap */
 
 #ifdef __cplusplus
 extern "C" {

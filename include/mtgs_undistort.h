@@ -18,7 +18,7 @@ extern "C" {
  * [RECALLED] cv2 was not available to run.  The rule below is OpenCV's as recalled, and it is THIS PROJECT'S DEFINITION: nothing
  * here claims byte equality with OpenCV.  tests/undistort_refs.py restates it in NumPy and pins it with known answers that do not
  * depend on the recall.  NOT covered: INTER_CUBIC (used only in front of UniDepth, generate_dense_depth.py:198-220), the rational,
- * thin-prism and tilt coefficients (more than five), adjust_brightness, decoding PNG files.
+ * thin-prism and tilt coefficients (more than five), decoding PNG files.  adjust_brightness is mtgs_brightness.h.
  *
  * cam: DEVICE double[MTGS_UNDISTORT_CAM_DOUBLES] = fx, fy, cx, cy (the source camera), fx', fy', cx', cy' (the new camera), k1, k2,
  * p1, p2, k3 (k3 = 0 for four coefficients).  It lives on the device so that a captured launch follows a camera written later.

@@ -29,9 +29,12 @@ split by the annotated boxes, painted and stacked into the background cloud and 
 voxel map, KISS-ICP in a canonical order: `KissConfig`, `VoxelMap`, `LidarOdometry`, `register_traversals`, `align_points_to_map`,
 `align_poses`, `registration_errors`), `mtgs_amd.undistort` (the lens undistortion of a training frame, one launch for every plane, by
 a rule the project defines: `optimal_new_camera_matrix`, `undistort_camera`, `undistort_plane`, `undistort_frame`, `undistort_map`,
-`UndistortCamera`).
+`UndistortCamera`), `mtgs_amd.brightness` (the cameras' brightness equalised: the V factors from the lidar overlap and the 8-bit HSV
+adjust of V, one launch for a batch of images, by a rule the project defines: `adjust_brightness`, `estimate_brightness_factors`,
+`pair_table`, `NUPLAN_PAIRS`; `SweepStack(equalise_brightness=True)`).
 """
 from .appearance import wild_color_source, wild_colors
+from .brightness import NUPLAN_PAIRS, adjust_brightness, estimate_brightness_factors, pair_table
 from .crop import OrientedBox, crop_gaussians
 from .densify import NodeRefine, RefineConfig, refine_scene
 from .dino import DinoConfig, DinoWeights, dino_similarity
@@ -63,4 +66,5 @@ __all__ = ["rasterization", "spherical_harmonics", "fully_fused_projection", "is
            "resize_plane", "resize_frame", "frame_masks", "masked_labels", "scaled_size",
            "split_sweep", "box_matrices", "SweepStack", "SplitSweep", "StackedClouds",
            "KissConfig", "VoxelMap", "LidarOdometry", "register_traversals", "align_points_to_map", "align_poses", "registration_errors",
-           "UndistortCamera", "optimal_new_camera_matrix", "undistort_camera", "undistort_plane", "undistort_frame", "undistort_map"]
+           "UndistortCamera", "optimal_new_camera_matrix", "undistort_camera", "undistort_plane", "undistort_frame", "undistort_map",
+           "adjust_brightness", "estimate_brightness_factors", "pair_table", "NUPLAN_PAIRS"]

@@ -44,11 +44,13 @@ COMMON_FLAGS = [
 # 27 sums of an iteration are compared bit for bit with a NumPy restatement.
 # undistort.hip (the lens undistortion of a frame) evaluates its map in fp64, one rounding per operation, before the rounding to
 # float32 and to five fractional bits: the map and every sampled byte are compared bit for bit with a NumPy restatement.
+# brightness.hip (the V factors and the HSV adjust) converts HSV to RGB in fp32 with one rounding per operation -- a fused
+# vf * (1 - sf * f) would change bytes -- and shares lidar.hip's fp64 sample, whose truncated V is compared bit for bit with the reference.
 PER_FILE_FLAGS = {"project.hip": ["-ffp-contract=off"], "front.hip": ["-ffp-contract=off"], "metrics.hip": ["-ffp-contract=off"],
                   "geomloss.hip": ["-ffp-contract=off"], "depthloss.hip": ["-ffp-contract=off"], "seed.hip": ["-ffp-contract=off"], "cloud.hip": ["-ffp-contract=off"],
                   "crop.hip": ["-ffp-contract=off"], "present.hip": ["-ffp-contract=off"], "lidar.hip": ["-ffp-contract=off"],
                   "frame.hip": ["-ffp-contract=off"], "stack.hip": ["-ffp-contract=off"], "icp.hip": ["-ffp-contract=off"],
-                  "undistort.hip": ["-ffp-contract=off"]}
+                  "undistort.hip": ["-ffp-contract=off"], "brightness.hip": ["-ffp-contract=off"]}
 
 
 class HipccNotFound(RuntimeError):

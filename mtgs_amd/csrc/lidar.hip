@@ -19,6 +19,7 @@
 //
 // Compiled with -ffp-contract=off: every product and sum rounds once, as the NumPy restatement of tests/lidar_refs.py does.
 #include "common.hpp"
+#include "lidar_sample.hpp"      // load_point, row34 and the per-camera sample that brightness.hip shares
 
 namespace {
 
@@ -31,15 +32,6 @@ struct Mat33 {
     double m[9];
 };
 
-template <class T>
-__device__ __forceinline__ void load_point(const T *__restrict__ points, int64_t stride, int64_t i, double x[3]) {
-    const T *p = points + i * stride;
-    x[0] = (double)p[0];
-    x[1] = (double)p[1];
-    x[2] = (double)p[2];
-}
-
-__device__ __forceinline__ double row34(const double *m, const double x[3]) { return ((m[0] * x[0] + m[1] * x[1]) + m[2] * x[2]) + m[3]; }
 __device__ __forceinline__ double row33(const double *m, const double c[3]) { return (m[0] * c[0] + m[1] * c[1]) + m[2] * c[2]; }
 
 // steps 1-6 of mtgs_lidar_depth: the pixel of x, or -1; *q2 is the depth the pixel would take
@@ -103,8 +95,6 @@ __global__ __launch_bounds__(TB) void depth_resolve_kernel(int32_t N, const T *_
     if (index) index[t] = i;
 }
 
-__device__ __forceinline__ int clampi(int v, int hi) { return v < 0 ? 0 : (v > hi ? hi : v); }
-
 template <class T>
 __global__ __launch_bounds__(TB) void paint_kernel(int32_t N, const T *__restrict__ points, int64_t stride, int C,
                                                    const double *__restrict__ mats, int h, int w, const uint8_t *__restrict__ images,
@@ -114,36 +104,18 @@ __global__ __launch_bounds__(TB) void paint_kernel(int32_t N, const T *__restric
     if (t >= N) return;
     double x[3];
     load_point(points, stride, t, x);
-    const double W = (double)w, H = (double)h, Wm1 = (double)(w - 1), Hm1 = (double)(h - 1);
     const int64_t plane = (int64_t)h * w;
     double sum[3] = {0.0, 0.0, 0.0};
     int32_t seen = 0, label = 0;
     for (int c = 0; c < C; ++c) {
-        const double *m = mats + 12 * c;                   // wave-uniform: scalar loads
-        const double p2 = row34(m + 8, x);
-        if (!(p2 > 0.1)) continue;
-        const double z = fmin(fmax(p2, 1e-5), 99999.0);
-        const double nx = (row34(m, x) / z) / W, ny = (row34(m + 4, x) / z) / H;
-        if (!(nx < 1.0 && nx >= 0.0 && ny < 1.0 && ny >= 0.0)) continue;
-        const double ix = (((nx * 2.0 - 1.0) + 1.0) / 2.0) * Wm1, iy = (((ny * 2.0 - 1.0) + 1.0) / 2.0) * Hm1;
+        double ix, iy;
+        if (!lidar_see(mats + 12 * c, x, h, w, ix, iy)) continue;          // wave-uniform matrix: scalar loads
         if (masks && seen == 0)
             label = masks[c * plane + (int64_t)clampi((int)nearbyint(iy), h - 1) * w + clampi((int)nearbyint(ix), w - 1)];
         if (images) {
-            const double xf = floor(ix), yf = floor(iy);
-            const double fx = ix - xf, fy = iy - yf;
-            // ix may round up to w - 1 itself: the neighbour beyond the image has weight 0 and is read at the edge instead
-            const int x0 = clampi((int)xf, w - 1), y0 = clampi((int)yf, h - 1), x1 = min(x0 + 1, w - 1), y1 = min(y0 + 1, h - 1);
-            const uint8_t *img = images + c * plane * 3;
-            const uint8_t *t00 = img + ((int64_t)y0 * w + x0) * 3, *t01 = img + ((int64_t)y0 * w + x1) * 3;
-            const uint8_t *t10 = img + ((int64_t)y1 * w + x0) * 3, *t11 = img + ((int64_t)y1 * w + x1) * 3;
-            const double w00 = (1.0 - fx) * (1.0 - fy), w01 = fx * (1.0 - fy), w10 = (1.0 - fx) * fy, w11 = fx * fy;
+            const LidarTaps taps = lidar_taps(images + c * plane * 3, h, w, ix, iy);
 #pragma unroll
-            for (int k = 0; k < 3; ++k) {
-                const int ch = reverse ? 2 - k : k;
-                const double v = (((double)t00[ch] / 255.0) * w00 + ((double)t01[ch] / 255.0) * w01) + ((double)t10[ch] / 255.0) * w10 +
-                                 ((double)t11[ch] / 255.0) * w11;
-                sum[k] = sum[k] + v;
-            }
+            for (int k = 0; k < 3; ++k) sum[k] = sum[k] + lidar_tap_value(taps, reverse ? 2 - k : k);
         }
         ++seen;
     }

@@ -18,9 +18,10 @@ is a gather through source indices that Pillow finds by repeated addition.  The 
 (mtgs_amd.dino's builders), uploaded with a blocking copy and kept per (source size, target size, device): call once before
 capturing a HIP graph.  No atomics, no host read; a whole frame is three launches (image, depth, all nearest planes).
 
-NOT covered, because nothing here can pin them: adjust_brightness (cv2's HSV round trip), decoding the depth PNG, and RGBA images
-(Pillow premultiplies alpha around the resize; nuPlan frames are RGB).  The cv2.remap undistortion in front of the resize is
-mtgs_amd.undistort, by a rule the project defines; its valid_mask, panoptic and semantic planes are what frame_masks takes.
+NOT covered, because nothing here can pin them: decoding the depth PNG, and RGBA images (Pillow premultiplies alpha around the
+resize; nuPlan frames are RGB).  The cv2.remap undistortion in front of the resize is mtgs_amd.undistort and adjust_brightness
+(cv2's HSV round trip) in front of that is mtgs_amd.brightness, both by rules the project defines; undistort's valid_mask, panoptic
+and semantic planes are what frame_masks takes.
 """
 from __future__ import annotations
 

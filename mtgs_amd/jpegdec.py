@@ -15,9 +15,9 @@ upsampling, 16-bit fixed-point colour) for what is accepted: 8-bit baseline sequ
 one interleaved scan, luma sampled 1x1 / 2x1 / 2x2 with chroma 1x1 ("4:4:4", "4:2:2", "4:2:0"), 8-bit quantisation tables, with or
 without restart markers and with any Huffman tables.  Everything else is refused by name with NotImplementedError, a file that is
 cut short with ValueError, both before any launch.  Exactness is claimed for files whose IDCT stays inside the library's sample
-range, which every file an encoder writes does.  The brightness adjustment of the reference's loader stays on the host: a dataset
-that needs it does not gain from this.  The undistortion (cv2.remap) takes the decoded pixels on the
-device: mtgs_amd.undistort, by a rule the project defines.
+range, which every file an encoder writes does.  The brightness adjustment of the reference's loader (a dataset with
+v_adjust_factors) and the undistortion (cv2.remap) take the decoded pixels on the device: mtgs_amd.brightness and mtgs_amd.undistort,
+by rules the project defines (INTEGRATION.md sections 23 and 22).
 
 From a DeviceJpeg, with `out` and `workspace` given, decode_jpeg makes no copy, no allocation and no host read.
 """

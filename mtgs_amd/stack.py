@@ -11,21 +11,23 @@ the point; it is an instance point if the tight test holds too and is dropped ot
     box_matrices(boxes)                                          -> (lidar2box [B, 4, 4], box2lidar [B, 4, 4], half_sizes [B, 3]), NumPy
     upload_boxes(boxes, include=None, fill_scale=0.25, device=)  -> BoxTable on the device (once per frame)
     split_sweep(points, boxes, include=None, fill_scale=0.25)    -> SplitSweep(points, offsets, slot)
-    stack_frame(points, table, lidar2imgs, images, sem_masks, channel_order="bgr", label_cutoff=10) -> FrameClouds
+    stack_frame(points, table, lidar2imgs, images, sem_masks, channel_order="bgr", label_cutoff=10, equalise_brightness=False) -> FrameClouds
     SweepStack(fill_scale=0.25, label_cutoff=10, skip_classes=...).add_frame(...) / .finish() -> StackedClouds
+    SweepStack(...).configure_brightness(equalise_brightness=True, pairs=NUPLAN_PAIRS): every frame's images equalised before the painting
 
 The box matrices are built on the host with the NumPy calls the reference uses (np.cos / np.sin, np.linalg.inv) and uploaded once per
 call; the kernels take matrices, never boxes.  A frame reads nothing back and can be captured in a HIP graph (given a BoxTable);
 `finish` makes one host read, of the totals that size its outputs.  All arithmetic is fp64 in the stated order; tests/stack_refs.py
 restates it in NumPy.
 
-Out of scope: parsing the .pcd sweeps and the `only_top` selection, `adjust_brightness` (OpenCV), and writing the .pcd files: the
-caller hands in the sweep and the undistorted images and takes device tensors back.  The undistortion itself (mode
-keep_focal_length, linear for the images, nearest for the masks) is mtgs_amd.undistort.undistort_plane, by a rule the project defines.
+Out of scope: parsing the .pcd sweeps and the `only_top` selection, and writing the .pcd files: the caller hands in the sweep and
+the undistorted images and takes device tensors back.  The undistortion itself (mode keep_focal_length, linear for the images,
+nearest for the masks) is mtgs_amd.undistort.undistort_plane, and the brightness equalisation between it and the painting
+(stack_RGB_point_cloud.py:81-87) is mtgs_amd.brightness, switched on by `equalise_brightness=`: both by rules the project defines.
 """
 from __future__ import annotations
 
-from typing import Dict, NamedTuple, Sequence, Tuple
+from typing import Dict, NamedTuple, Optional, Sequence, Tuple
 
 import numpy as np
 import torch
@@ -35,6 +37,7 @@ from . import _abi
 from ._inputs import point_rows, row_stride, shape_of
 from ._lib import call, ptr, require_gpu, stream_of, workspace
 from . import lidar as _lidar
+from .brightness import NUPLAN_PAIRS, adjust_brightness, estimate_brightness_factors
 
 _ABI = _abi.header_abi("mtgs_stack.h")
 MAX_BOXES = _ABI.constants["MTGS_STACK_MAX_BOXES"]
@@ -199,19 +202,27 @@ def _cameras(lidar2imgs, images, sem_masks, channel_order):
 
 
 def stack_frame(points: Tensor, table: BoxTable, lidar2imgs: Tensor, images: Tensor, sem_masks: Tensor, channel_order: str = "bgr",
-                label_cutoff: int = 10) -> FrameClouds:
+                label_cutoff: int = 10, equalise_brightness: bool = False, brightness_pairs=NUPLAN_PAIRS,
+                brightness_points: Optional[Tensor] = None) -> FrameClouds:
     """One frame of the stack (stack_RGB_point_cloud.py:91-126): `split_sweep`, the cameras' colours and labels of the background
     points and of the instance points taken back to the lidar frame (`lidar.paint_points`' kernel and arguments), and the rows some
     camera sees, group by group, order kept.  Everything stays on the device at the sweep's capacity N; nothing is read back, so the
-    call can be captured in a HIP graph."""
+    call can be captured in a HIP graph.  equalise_brightness (off by default, and then nothing changes): the images first go through
+    `brightness.estimate_brightness_factors` (over brightness_points, the reference's combined sweep, or over `points` when None;
+    brightness_pairs as that function takes them) and `brightness.adjust_brightness`, as stack_RGB_point_cloud.py:81-87 has it."""
     p = _sweep(points)
     if not isinstance(table, BoxTable):
         raise TypeError(f"table must be a BoxTable (upload_boxes), got {type(table).__name__}")
     C, h, w = _cameras(lidar2imgs, images, sem_masks, channel_order)
     if isinstance(label_cutoff, bool) or not isinstance(label_cutoff, int):
         raise ValueError(f"label_cutoff must be an integer, got {label_cutoff!r}")
+    if not isinstance(equalise_brightness, bool):
+        raise ValueError(f"equalise_brightness must be True or False, got {equalise_brightness!r}")
     require_gpu(points, *table, lidar2imgs, images, sem_masks)
     dev, N, B = p.device, p.shape[0], table.lidar2box.shape[0]
+    if equalise_brightness:
+        factors = estimate_brightness_factors(p if brightness_points is None else brightness_points, lidar2imgs, images, brightness_pairs)
+        images = adjust_brightness(images, factors, channel_order)
     m = _lidar._rows34(lidar2imgs)
     img, msk = images.detach().contiguous(), sem_masks.detach().contiguous()
     out = torch.empty((N, 3), dtype=torch.float64, device=dev)
@@ -233,7 +244,11 @@ class SweepStack:
     """The traversal: `add_frame` per frame in frame order (device work only), `finish` once (one host read).
 
     fill_scale: the margin around a box (split_points' 0.25); label_cutoff: the background keeps labels below it (`< 10` drops sky,
-    person, rider and the vehicles); skip_classes: the box classes that take no points."""
+    person, rider and the vehicles); skip_classes: the box classes that take no points.  `configure_brightness` switches the
+    equalisation of every frame's images on (`stack_frame(equalise_brightness=True)`); it is off by default, and off is what the stack
+    computed before the option existed."""
+
+    equalise_brightness, brightness_pairs = False, NUPLAN_PAIRS
 
     def __init__(self, fill_scale: float = 0.25, label_cutoff: int = 10, skip_classes: Sequence[str] = SKIP_CLASSES):
         if isinstance(label_cutoff, bool) or not isinstance(label_cutoff, int):
@@ -246,6 +261,16 @@ class SweepStack:
 
     def __len__(self) -> int:
         return len(self._frames)
+
+    def configure_brightness(self, equalise_brightness: bool = True, pairs=NUPLAN_PAIRS) -> "SweepStack":
+        """equalise_brightness=True: from the next frame on the images go through `brightness.estimate_brightness_factors` (over the
+        frame's own sweep, with `pairs`) and `brightness.adjust_brightness` in front of the painting, as stack_RGB_point_cloud.py:81-87
+        has it (the reference estimates from the combined sweep of all lidars: `stack_frame(brightness_points=)` takes one).  Returns
+        self: `SweepStack().configure_brightness(equalise_brightness=True)`."""
+        if not isinstance(equalise_brightness, bool):
+            raise ValueError(f"equalise_brightness must be True or False, got {equalise_brightness!r}")
+        self.equalise_brightness, self.brightness_pairs = equalise_brightness, tuple(tuple(int(v) for v in row) for row in pairs)
+        return self
 
     def add_frame(self, points: Tensor, boxes, names: Sequence[str], track_tokens: Sequence[str], lidar2global, lidar2imgs: Tensor,
                   images: Tensor, sem_masks: Tensor, channel_order: str = "bgr") -> FrameClouds:
@@ -268,7 +293,8 @@ class SweepStack:
         if self._device is not None and p.device != self._device:
             raise ValueError(f"every frame must be on one device, got {p.device} after {self._device}")
         table = upload_boxes(b, include, self.fill_scale, p.device)
-        frame = stack_frame(p, table, lidar2imgs, images, sem_masks, channel_order, self.label_cutoff)
+        frame = stack_frame(p, table, lidar2imgs, images, sem_masks, channel_order, self.label_cutoff, self.equalise_brightness,
+                            self.brightness_pairs)
         self._device = p.device
         self._frames.append((frame, g[:3].astype(np.float64), [(1 + i, tokens[i]) for i in range(len(tokens)) if include[i]]))
         return frame

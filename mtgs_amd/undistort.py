@@ -18,7 +18,8 @@ own -- and, to the kernel, a map of its own (`_launch(..., map=)`).  Sizes are (
 argument is (width, height).
 
 NOT covered: cubic interpolation (used only in front of UniDepth, generate_dense_depth.py:198-220), more than five distortion
-coefficients (rational, thin-prism, tilt), adjust_brightness, decoding PNG files, RGBA images.
+coefficients (rational, thin-prism, tilt), decoding PNG files, RGBA images.  adjust_brightness, which the dataset runs in front of
+the undistortion and the point stack behind it, is mtgs_amd.brightness.
 """
 from __future__ import annotations
 

@@ -31,12 +31,15 @@ voxel map, KISS-ICP in a canonical order: `KissConfig`, `VoxelMap`, `LidarOdomet
 a rule the project defines: `optimal_new_camera_matrix`, `undistort_camera`, `undistort_plane`, `undistort_frame`, `undistort_map`,
 `UndistortCamera`), `mtgs_amd.brightness` (the cameras' brightness equalised: the V factors from the lidar overlap and the 8-bit HSV
 adjust of V, one launch for a batch of images, by a rule the project defines: `adjust_brightness`, `estimate_brightness_factors`,
-`pair_table`, `NUPLAN_PAIRS`; `SweepStack(equalise_brightness=True)`).
+`pair_table`, `NUPLAN_PAIRS`; `SweepStack(equalise_brightness=True)`), `mtgs_amd.evaldump` (the evaluation image dump: a rendered frame
+bent back into the raw camera and encoded, by a rule the project defines: `redistort_image`, `redistort_map`, `eval_dump`,
+`eval_dump_paths`).
 """
 from .appearance import wild_color_source, wild_colors
 from .brightness import NUPLAN_PAIRS, adjust_brightness, estimate_brightness_factors, pair_table
 from .crop import OrientedBox, crop_gaussians
 from .densify import NodeRefine, RefineConfig, refine_scene
+from .evaldump import eval_dump, eval_dump_paths
 from .dino import DinoConfig, DinoWeights, dino_similarity
 from .frame import frame_masks, masked_labels, resize_frame, resize_plane, scaled_size
 from .jpeg import JpegStream, encode_jpeg
@@ -50,8 +53,8 @@ from .registration import (KissConfig, LidarOdometry, VoxelMap, align_points_to_
                            registration_errors)
 from .rendering import rasterization
 from .seed import knn_distances, seed_gaussians, sky_points
-from .undistort import (UndistortCamera, optimal_new_camera_matrix, undistort_camera, undistort_frame, undistort_map,
-                        undistort_plane)
+from .undistort import (UndistortCamera, optimal_new_camera_matrix, redistort_image, redistort_map, undistort_camera, undistort_frame,
+                        undistort_map, undistort_plane)
 from .stack import SplitSweep, StackedClouds, SweepStack, box_matrices, split_sweep
 from .wrapper import (exact_lists, fully_fused_projection, graph_mode, isect_offset_encode, isect_tiles, lists_are_tight,
                       rasterize_to_pixels, sh_lazy, sh_prefill, spherical_harmonics, tight_lists)
@@ -67,4 +70,5 @@ __all__ = ["rasterization", "spherical_harmonics", "fully_fused_projection", "is
            "split_sweep", "box_matrices", "SweepStack", "SplitSweep", "StackedClouds",
            "KissConfig", "VoxelMap", "LidarOdometry", "register_traversals", "align_points_to_map", "align_poses", "registration_errors",
            "UndistortCamera", "optimal_new_camera_matrix", "undistort_camera", "undistort_plane", "undistort_frame", "undistort_map",
-           "adjust_brightness", "estimate_brightness_factors", "pair_table", "NUPLAN_PAIRS"]
+           "adjust_brightness", "estimate_brightness_factors", "pair_table", "NUPLAN_PAIRS",
+           "redistort_image", "redistort_map", "eval_dump", "eval_dump_paths"]

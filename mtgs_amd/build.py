@@ -46,11 +46,13 @@ COMMON_FLAGS = [
 # float32 and to five fractional bits: the map and every sampled byte are compared bit for bit with a NumPy restatement.
 # brightness.hip (the V factors and the HSV adjust) converts HSV to RGB in fp32 with one rounding per operation -- a fused
 # vf * (1 - sf * f) would change bytes -- and shares lidar.hip's fp64 sample, whose truncated V is compared bit for bit with the reference.
+# redistort.hip (a rendered frame bent back into the raw camera) iterates the inverse lens model in fp64, one rounding per operation:
+# its map and every sampled byte are compared bit for bit with a NumPy restatement, as undistort.hip's are.
 PER_FILE_FLAGS = {"project.hip": ["-ffp-contract=off"], "front.hip": ["-ffp-contract=off"], "metrics.hip": ["-ffp-contract=off"],
                   "geomloss.hip": ["-ffp-contract=off"], "depthloss.hip": ["-ffp-contract=off"], "seed.hip": ["-ffp-contract=off"], "cloud.hip": ["-ffp-contract=off"],
                   "crop.hip": ["-ffp-contract=off"], "present.hip": ["-ffp-contract=off"], "lidar.hip": ["-ffp-contract=off"],
                   "frame.hip": ["-ffp-contract=off"], "stack.hip": ["-ffp-contract=off"], "icp.hip": ["-ffp-contract=off"],
-                  "undistort.hip": ["-ffp-contract=off"], "brightness.hip": ["-ffp-contract=off"]}
+                  "undistort.hip": ["-ffp-contract=off"], "brightness.hip": ["-ffp-contract=off"], "redistort.hip": ["-ffp-contract=off"]}
 
 
 class HipccNotFound(RuntimeError):

@@ -21,6 +21,7 @@
 // the categories are clamped to what 8-bit samples can reach (11 for a DC difference, 10 for an AC coefficient).
 #include "common.hpp"
 #include "jpeg_zigzag.hpp"
+#include "sample_u8.hpp"
 #include "scan.hpp"
 
 namespace {
@@ -182,15 +183,6 @@ __device__ __forceinline__ void dct8(int *d) {
     d[5] = descale(a5 + z2 + z4, LOW);
     d[3] = descale(a6 + z2 + z3, LOW);
     d[1] = descale(a7 + z1 + z4, LOW);
-}
-
-__device__ __forceinline__ int load_sample(const void *image, bool is_float, bool round, int64_t at) {
-    if (!is_float) return ((const uint8_t *)image)[at];
-    float x = ((const float *)image)[at];
-    x = x != x ? 0.f : (x < 0.f ? 0.f : (x > 1.f ? 1.f : x));
-    x = __fmul_rn(x, 255.f);                 // two roundings, as mtgs_present.h's formats: never one fused multiply-add
-    if (round) x = __fadd_rn(x, 0.5f);
-    return (int)(uint32_t)x;
 }
 
 constexpr int fix16(double x) { return (int)(x * 65536 + 0.5); }

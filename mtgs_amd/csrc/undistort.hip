@@ -9,11 +9,11 @@
 // below what the loads cost) and walks the plane table, which lives in the kernel's arguments: the plane loop and the branch on
 // the operation are wave-uniform.  Nothing but the planes is read or written: no map in memory, unless the caller passes one.
 #include "common.hpp"
+#include "remap_linear.hpp"
 
 namespace {
 
-constexpr int TW = MTGS_UNDISTORT_TILE_W, TH = MTGS_UNDISTORT_TILE_H, NT = TW * TH, MAXC = 3;
-static_assert(TW == MTGS_WAVE && NT <= 1024, "a wave is one row of a tile");
+constexpr int NT = REMAP_NT, MAXC = 3;
 
 struct PlaneTable {
     mtgs_undistort_plane p[MTGS_UNDISTORT_MAX_PLANES];
@@ -33,19 +33,10 @@ __device__ __forceinline__ void map_of(const double *__restrict__ cam, int i, in
     mapy = (float)(fy * yd + cy);
 }
 
-// an integral float32 coordinate as an int; anything with !(|f| < 2^30), non-finite included, becomes a coordinate far outside
-__device__ __forceinline__ int coord(float f) { return fabsf(f) < 1073741824.0f ? (int)f : -(1 << 30); }
-
-__device__ __forceinline__ bool pixel_of(int oh, int ow, int &i, int &j) {
-    j = (int)blockIdx.x * TW + (int)(threadIdx.x % TW);
-    i = (int)blockIdx.y * TH + (int)(threadIdx.x / TW);
-    return i < oh && j < ow;
-}
-
 __global__ __launch_bounds__(NT) void undistort_frame_kernel(PlaneTable t, int h, int w, int oh, int ow, const double *__restrict__ cam,
                                                              const float *__restrict__ map) {
     int i, j;
-    if (!pixel_of(oh, ow, i, j)) return;
+    if (!remap_pixel_of(oh, ow, i, j)) return;
     const int64_t at = (int64_t)i * ow + j;
     float mapx, mapy;
     if (map != nullptr) {
@@ -55,25 +46,22 @@ __global__ __launch_bounds__(NT) void undistort_frame_kernel(PlaneTable t, int h
         map_of(cam, i, j, mapx, mapy);
     }
     // INTER_NEAREST: the source pixel, or none
-    const int nx = coord(rintf(mapx)), ny = coord(rintf(mapy));
+    const int nx = remap_coord(rintf(mapx)), ny = remap_coord(rintf(mapy));
     const bool inside = nx >= 0 && nx < w && ny >= 0 && ny < h;
     // INTER_LINEAR: five fractional bits, four taps, each inside or zero
-    const int sx = coord(rintf(__fmul_rn(mapx, 32.0f))), sy = coord(rintf(__fmul_rn(mapy, 32.0f)));
-    const int ix = sx >> 5, iy = sy >> 5, a = sx & 31, b = sy & 31;
-    const bool x0 = ix >= 0 && ix < w, x1 = ix + 1 >= 0 && ix + 1 < w, y0 = iy >= 0 && iy < h, y1 = iy + 1 >= 0 && iy + 1 < h;
-    const int w00 = (32 - a) * (32 - b) * 32, w01 = a * (32 - b) * 32, w10 = (32 - a) * b * 32, w11 = a * b * 32;
+    const LinearTaps f = linear_taps(mapx, mapy, h, w);
 
     for (int q = 0; q < t.n; ++q) {
         const mtgs_undistort_plane &p = t.p[q];
         const int64_t s0 = p.src_stride[0], s1 = p.src_stride[1], s2 = p.src_stride[2];
         if (p.op == MTGS_UNDISTORT_LINEAR) {
             const uint8_t *s = (const uint8_t *)p.src;
-            const int64_t o00 = (int64_t)iy * s0 + (int64_t)ix * s1;
+            const int64_t o00 = (int64_t)f.iy * s0 + (int64_t)f.ix * s1;
             for (int k = 0; k < p.channels; ++k) {
                 const int64_t o = o00 + k * s2;
-                const int v00 = (y0 && x0) ? s[o] : 0, v01 = (y0 && x1) ? s[o + s1] : 0;
-                const int v10 = (y1 && x0) ? s[o + s0] : 0, v11 = (y1 && x1) ? s[o + s0 + s1] : 0;
-                const int v = (w00 * v00 + w01 * v01 + w10 * v10 + w11 * v11 + 16384) >> 15;
+                const int v00 = (f.y0 && f.x0) ? s[o] : 0, v01 = (f.y0 && f.x1) ? s[o + s1] : 0;
+                const int v10 = (f.y1 && f.x0) ? s[o + s0] : 0, v11 = (f.y1 && f.x1) ? s[o + s0 + s1] : 0;
+                const int v = linear_blend(f, v00, v01, v10, v11);
                 if (p.out_float) ((float *)p.dst)[at * p.channels + k] = __fdiv_rn((float)v, 255.0f);
                 else ((uint8_t *)p.dst)[at * p.channels + k] = (uint8_t)v;
             }
@@ -96,7 +84,7 @@ __global__ __launch_bounds__(NT) void undistort_frame_kernel(PlaneTable t, int h
 
 __global__ __launch_bounds__(NT) void undistort_map_kernel(int oh, int ow, const double *__restrict__ cam, float2 *__restrict__ map) {
     int i, j;
-    if (!pixel_of(oh, ow, i, j)) return;
+    if (!remap_pixel_of(oh, ow, i, j)) return;
     float mapx, mapy;
     map_of(cam, i, j, mapx, mapy);
     map[(int64_t)i * ow + j] = make_float2(mapx, mapy);
@@ -106,8 +94,6 @@ int check_size(const char *fn, const char *name, int v) {
     MTGS_REQUIRE(v >= 1 && v <= MTGS_UNDISTORT_MAX_SIZE, MTGS_EINVAL, "%s: %s outside [1, %d] (%d)", fn, name, MTGS_UNDISTORT_MAX_SIZE, v);
     return MTGS_OK;
 }
-
-dim3 tiles(int oh, int ow) { return dim3((unsigned)ceil_div64(ow, TW), (unsigned)ceil_div64(oh, TH)); }
 
 }  // namespace
 
@@ -144,7 +130,7 @@ extern "C" int mtgs_undistort_frame(int h, int w, int oh, int ow, const double *
         }
         t.p[q] = p;
     }
-    undistort_frame_kernel<<<tiles(oh, ow), NT, 0, (hipStream_t)stream>>>(t, h, w, oh, ow, cam, map);
+    undistort_frame_kernel<<<remap_tiles(oh, ow), NT, 0, (hipStream_t)stream>>>(t, h, w, oh, ow, cam, map);
     MTGS_CHECK_LAUNCH(fn);
     return MTGS_OK;
 }
@@ -156,7 +142,7 @@ extern "C" int mtgs_undistort_map(int oh, int ow, const double *cam, float *map,
     MTGS_NONNULL(fn, cam); MTGS_NONNULL(fn, map);
     MTGS_REQUIRE(((uintptr_t)cam & 7) == 0, MTGS_EINVAL, "%s: cam must be 8-byte aligned", fn);
     MTGS_REQUIRE(((uintptr_t)map & 7) == 0, MTGS_EINVAL, "%s: map must be 8-byte aligned", fn);
-    undistort_map_kernel<<<tiles(oh, ow), NT, 0, (hipStream_t)stream>>>(oh, ow, cam, (float2 *)map);
+    undistort_map_kernel<<<remap_tiles(oh, ow), NT, 0, (hipStream_t)stream>>>(oh, ow, cam, (float2 *)map);
     MTGS_CHECK_LAUNCH(fn);
     return MTGS_OK;
 }

@@ -11,6 +11,12 @@ camera is prepared once and a frame is ONE launch that evaluates the map per pix
     undistort_frame(cam, image=None, ego_mask=None, panoptic=None, semantic=None, image_float=False) -> dict
     undistort_map(cam) -> float32 [H, W, 2]
 
+and the way back, for the evaluation dump in image_saving_mode = "nuplan" (include/mtgs_redistort.h, csrc/redistort.hip; DESIGN.md
+section 24; mtgs_amd.evaldump strings it to the JPEG encoder) -- the same camera, the roles of its two sizes swapped:
+
+    redistort_image(image, cam, iterations=5, conversion="truncate", map=None, out=None) -> uint8 [H_raw, W_raw, C]
+    redistort_map(cam, iterations=5) -> float32 [H_raw, W_raw, 2]
+
 [RECALLED] cv2 was not available to run.  The rule is OpenCV's as recalled and is this project's DEFINITION (the header states it in
 full; tests/undistort_refs.py restates it in NumPy and pins it with known answers that need no recall); nothing here claims byte
 equality with OpenCV.  Because the recalled getOptimalNewCameraMatrix cannot be checked, a caller may always pass a `new_K` of its
@@ -31,10 +37,12 @@ import torch
 from torch import Tensor
 
 from ._abi import header_abi
-from ._inputs import image_plane, image_size
+from ._inputs import image_plane, image_size, shape_of
 from ._lib import call, ptr, require_gpu
 
 _ABI = header_abi("mtgs_undistort.h")
+MAX_ITERATIONS = header_abi("mtgs_redistort.h").constants["MTGS_REDISTORT_MAX_ITERATIONS"]
+_CONVERSIONS = {k: header_abi("mtgs_present.h").constants["MTGS_PRESENT_U8_" + k.upper()] for k in ("truncate", "round")}
 _PLANE = _ABI.structs["mtgs_undistort_plane"]
 TILE_W, TILE_H = _ABI.constants["MTGS_UNDISTORT_TILE_W"], _ABI.constants["MTGS_UNDISTORT_TILE_H"]
 MAX_PLANES = _ABI.constants["MTGS_UNDISTORT_MAX_PLANES"]
@@ -284,5 +292,80 @@ def undistort_map(cam: UndistortCamera) -> Tensor:
     return out
 
 
+# ---- the way back: a rendered frame into the raw camera (include/mtgs_redistort.h) --------------------------
+def _check_iterations(iterations) -> int:
+    if isinstance(iterations, bool) or not isinstance(iterations, int) or not 0 <= iterations <= MAX_ITERATIONS:
+        raise ValueError(f"iterations must be an integer in [0, {MAX_ITERATIONS}], got {iterations!r}")
+    return iterations
+
+
+def _check_redistort_map(map, cam: UndistortCamera) -> None:
+    want = cam.source_size + (2,)
+    if not isinstance(map, Tensor) or map.dtype != torch.float32 or tuple(map.shape) != want or not map.is_contiguous():
+        got = f"{map.dtype} {tuple(map.shape)}" if isinstance(map, Tensor) else type(map).__name__
+        raise ValueError(f"map must be a contiguous float32 {want} tensor (redistort_map), got {got}")
+    if map.device != cam.device:
+        raise RuntimeError(f"cam is on {cam.device}, map on {map.device}")
+
+
+def _launch_redistort(cam: UndistortCamera, src: int, src_float: bool, strides, channels: int, out: Tensor, iterations: int,
+                      conversion: str, map: Optional[Tensor], stream) -> None:
+    """mtgs_redistort_frame on a source given as its base address and its (row, column, channel) strides in elements"""
+    (h, w), (oh, ow) = cam.size, cam.source_size            # the roles are swapped: the new camera's image is read, the raw one written
+    call("mtgs_redistort_frame", h, w, oh, ow, ptr(cam.params), iterations, ptr(map), src, int(src_float), _CONVERSIONS[conversion],
+         *strides, channels, ptr(out), stream)
+
+
+def redistort_map(cam: UndistortCamera, iterations: int = 5) -> Tensor:
+    """float32 [H_raw, W_raw, 2] = (mapx, mapy): where each pixel of the RAW image lies in the undistorted one
+    (initInverseRectificationMap(K, D, None, K', size) as `iterations` fixed-point iterations of the inverse lens model, in the form
+    of include/mtgs_redistort.h [RECALLED]).  Pass it to redistort_image(map=) to read the map instead of evaluating it."""
+    _check_cam(cam)
+    iterations = _check_iterations(iterations)
+    require_gpu(cam.params)
+    out = torch.empty(cam.source_size + (2,), dtype=torch.float32, device=cam.device)
+    call("mtgs_redistort_map", cam.source_size[0], cam.source_size[1], ptr(cam.params), iterations, ptr(out),
+         torch.cuda.current_stream(cam.device).cuda_stream)
+    return out
+
+
+def redistort_image(image: Tensor, cam: UndistortCamera, iterations: int = 5, conversion: str = "truncate", map: Optional[Tensor] = None,
+                    out: Optional[Tensor] = None) -> Tensor:
+    """invert_distortion (mtgs/utils/camera_utils.py:340-356) on the device, by the project's rule [RECALLED]: `image`, uint8 or
+    float32 [H, W, C] (C = 1 or 3, any strides) in the geometry of cam.size -- a rendered frame -- becomes uint8 [H_raw, W_raw, C] in
+    the raw camera's geometry (cam.source_size), ONE launch.  `cam` is undistort_camera's, unchanged: it holds exactly the camera pair
+    invert_distortion builds.  float32 is converted tap by tap as encode_jpeg converts ("truncate" is the evaluation dump's
+    (x * 255).astype(uint8), "round" adds 0.5 first), then sampled with the 8-bit linear rule of undistort_plane; outside the image
+    the value is 0.  `iterations` in [0, MAX_ITERATIONS]: 5 is the recalled rule and is up to 0.82 px off at the corners of a
+    nuPlan-like lens (20: 2.2e-7 px; the header has the table); 0 is the plain change of camera.  `map` (redistort_map's, or the
+    caller's own) is read instead of evaluating the iteration; `out` is written in place."""
+    _check_cam(cam)
+    iterations = _check_iterations(iterations)
+    if conversion not in _CONVERSIONS:
+        raise ValueError(f"conversion must be 'truncate' or 'round', got {conversion!r}")
+    if isinstance(image, Tensor) and image.dim() == 3 and image.shape[2] == 4:
+        raise NotImplementedError("image has 4 channels: RGBA images are not implemented (rendered frames are RGB)")
+    if not isinstance(image, Tensor) or image.dim() != 3:
+        raise ValueError(f"image must be [H, W, C], got {shape_of(image)}")
+    v, _ = image_plane(image, "image", (torch.uint8, torch.float32), channels=(1, 3))
+    if tuple(v.shape[:2]) != cam.size:
+        raise ValueError(f"image must be {cam.size[0]} x {cam.size[1]}, the camera's size, got {tuple(image.shape)}")
+    if v.device != cam.device:
+        raise RuntimeError(f"cam is on {cam.device}, image on {v.device}")
+    if map is not None:
+        _check_redistort_map(map, cam)
+    want = cam.source_size + (v.shape[2],)
+    if out is not None:
+        if not isinstance(out, Tensor) or out.dtype != torch.uint8 or tuple(out.shape) != want or not out.is_contiguous() or out.device != v.device:
+            got = f"{out.dtype} {tuple(out.shape)} on {out.device}" if isinstance(out, Tensor) else type(out).__name__
+            raise ValueError(f"out must be a contiguous uint8 {want} tensor on {v.device}, got {got}")
+    require_gpu(v)
+    if out is None:
+        out = torch.empty(want, dtype=torch.uint8, device=v.device)
+    _launch_redistort(cam, v.data_ptr(), v.dtype == torch.float32, v.stride(), v.shape[2], out, iterations, conversion, map,
+                      torch.cuda.current_stream(v.device).cuda_stream)
+    return out
+
+
 __all__ = ["optimal_new_camera_matrix", "undistort_camera", "undistort_plane", "undistort_frame", "undistort_map", "UndistortCamera",
-           "TILE_W", "TILE_H", "MAX_PLANES", "MAX_SIZE"]
+           "redistort_map", "redistort_image", "TILE_W", "TILE_H", "MAX_PLANES", "MAX_SIZE", "MAX_ITERATIONS"]

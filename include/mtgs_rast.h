@@ -47,6 +47,7 @@
 #include "mtgs_undistort.h"   /* a block of its own: lens undistortion of a training frame: the fp64 map, 8-bit linear and nearest remap, the valid mask */
 #include "mtgs_brightness.h"  /* a block of its own: camera brightness equalisation: the 8-bit HSV adjust of V and the per-camera factors from the lidar overlap */
 #include "mtgs_redistort.h"   /* a block of its own: a rendered frame bent back into the raw camera: the iterated fp64 inverse map and the 8-bit linear remap */
+#include "mtgs_png.h"   /* a block of its own: depth and label planes as indexed PNG: a writer every reader accepts, a parallel reader of its files */
 
 #ifdef __cplusplus
 extern "C" {

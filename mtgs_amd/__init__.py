@@ -33,7 +33,9 @@ a rule the project defines: `optimal_new_camera_matrix`, `undistort_camera`, `un
 adjust of V, one launch for a batch of images, by a rule the project defines: `adjust_brightness`, `estimate_brightness_factors`,
 `pair_table`, `NUPLAN_PAIRS`; `SweepStack(equalise_brightness=True)`), `mtgs_amd.evaldump` (the evaluation image dump: a rendered frame
 bent back into the raw camera and encoded, by a rule the project defines: `redistort_image`, `redistort_map`, `eval_dump`,
-`eval_dump_paths`).
+`eval_dump_paths`), `mtgs_amd.png` (depth and label planes as indexed PNG: a writer every PNG reader accepts and a parallel reader of
+its files, with the reference's two depth rules fused in: `encode_png`, `encode_depth_png`, `PngStream`, `parse_png`, `upload_png`,
+`decode_png`, `decode_depth_png`, `DevicePng`, `PngInfo`).
 """
 from .appearance import wild_color_source, wild_colors
 from .brightness import NUPLAN_PAIRS, adjust_brightness, estimate_brightness_factors, pair_table
@@ -48,6 +50,7 @@ from .lidar import PaintedPoints, depth_image, paint_points
 from .lpips import LpipsWeights
 from .metrics import color_correct, image_metrics
 from .present import ColormapOptions, colorize, colorize_depth, render_frame, viewer_depth, viewer_frame
+from .png import DevicePng, PngInfo, PngStream, decode_depth_png, decode_png, encode_depth_png, encode_png, parse_png, upload_png
 from .pointcloud import prepare_seed_cloud, statistical_outlier_removal, voxel_down_sample
 from .registration import (KissConfig, LidarOdometry, VoxelMap, align_points_to_map, align_poses, register_traversals,
                            registration_errors)
@@ -71,4 +74,5 @@ __all__ = ["rasterization", "spherical_harmonics", "fully_fused_projection", "is
            "KissConfig", "VoxelMap", "LidarOdometry", "register_traversals", "align_points_to_map", "align_poses", "registration_errors",
            "UndistortCamera", "optimal_new_camera_matrix", "undistort_camera", "undistort_plane", "undistort_frame", "undistort_map",
            "adjust_brightness", "estimate_brightness_factors", "pair_table", "NUPLAN_PAIRS",
-           "redistort_image", "redistort_map", "eval_dump", "eval_dump_paths"]
+           "redistort_image", "redistort_map", "eval_dump", "eval_dump_paths",
+           "encode_png", "encode_depth_png", "PngStream", "parse_png", "upload_png", "decode_png", "decode_depth_png", "DevicePng", "PngInfo"]
